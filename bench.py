@@ -10,6 +10,12 @@ one process per GPU, RCCL all-gather of the particle weights, all-to-all of migr
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus N ...                      starts its own N ranks (torch.distributed.run, one per GPU)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps and prints the headline line. `--full` adds everything else the line can
+carry: per-kernel HIP events, the isolated launches and the roofline / VALU-issue figures, the other modes and configs, the
+CPU baseline, the sharded step's phases and RCCL probes (N > 1), the single-handle comparison (--single-process).
+`--dump-outputs DIR` writes what the last timed step computed (the arrays a caller of SlamUpdate reads back) as .npy files
+(bench_outputs/ is kept out of git for them: `--dump-outputs bench_outputs/<build>`).
 """
 import argparse
 import ctypes as C
@@ -50,6 +56,37 @@ def committed_source(relpath):
     return {"file": relpath, "git_blob": blob, "measured_in_this_run": False}
 
 
+DUMP_MAP_PARTICLES = 256   # particles whose maps --dump-outputs writes (a fixed, seeded sample: all 2048 maps of config B are ~130 MB)
+
+
+def dump_outputs(nav, outdir, suffix="", map_particles=DUMP_MAP_PARTICLES):
+    """--dump-outputs: what a caller of the timed step reads back after its last step, as float64 .npy files. In frozen mode
+    the handle's getters report the last step's result. Particle weights, best particle, resample sources, poses, the best
+    particle's map and the maps of `map_particles` particles drawn with a fixed seed (components concatenated in the
+    handle's order, `map_counts` per particle); about 17 MB at config B."""
+    os.makedirs(outdir, exist_ok=True)
+    nav.sync()
+    out = {}
+    w = nav.VehicleWeights
+    src, resampled = nav.resample_sources()
+    best = nav.BestParticle
+    out["vehicle_weights"] = w
+    out["best_particle"] = np.array([best])
+    out["resample_sources"] = src
+    out["resampled"] = np.array([resampled])
+    out["poses"] = nav.poses()
+    out["best_map_weights"], out["best_map_means"], out["best_map_covs"] = nav.MapModel(best)
+    sample = np.sort(np.random.default_rng(20261016).choice(len(w), size=min(len(w), map_particles), replace=False))
+    maps = [nav.MapModel(int(i)) for i in sample]
+    out["map_particles"] = sample
+    out["map_counts"] = np.array([len(m[0]) for m in maps])
+    out["map_weights"] = np.concatenate([m[0] for m in maps])
+    out["map_means"] = np.concatenate([m[1] for m in maps])
+    out["map_covs"] = np.concatenate([m[2] for m in maps])
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -82,7 +119,16 @@ def parse():
                     help="N GPUs behind ONE handle in this process (phd_create_multi: peer copies instead of RCCL, the path a C# host drives); "
                          "2048 particles per device as in the sharded run")
     ap.add_argument("--devices", default="", help="with --single-process: the HIP ordinals, comma separated (default 0..N-1; a device may repeat: rehearsal on one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel HIP events (roofline, VALU issue), the extra legs of the N = 1 run, the CPU "
+                         "baseline, the sharded step's phases and RCCL probes, the single-handle comparison of --single-process (--no-* narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (weights, resample sources, poses, best map, a seeded sample of the maps) "
+                         "as float64 DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def launch_ranks(args):
@@ -468,7 +514,8 @@ def main():
     for _ in range(PREROLL_STEPS + args.warmup):
         step()
     barrier()
-    nav.timing_reset(0 if args.no_events else max(1, min(args.events_every, 255)))
+    events = args.full and not args.no_events
+    nav.timing_reset(max(1, min(args.events_every, 255)) if events else 0)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -479,9 +526,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    kernels = nav.last_timings()
+    kernels = nav.last_timings() if events else {}
     launches = nav.last_timing_counts() if kernels else {}
-    if use_dist and not args.host_plan:
+    if args.dump_outputs:
+        dump_outputs(nav, args.dump_outputs, "_rank%d" % rank if world > 1 else "", max(1, DUMP_MAP_PARTICLES // world))
+    if args.full and use_dist and not args.host_plan:
         # per-phase device time of the sharded step (torch events on the stream, 16 steps behind the timed region), and
         # what the collectives cost on this node, alone on the stream
         phase_ev = []
@@ -516,7 +565,7 @@ def main():
     #     In the timed region the two particle halves run on concurrent streams, so an event pair there also spans the
     #     other half's kernels; the roofline figure is taken from these non-overlapped launches.
     iso, iso_ms = {}, None
-    extra = world == 1 and not use_dist and not args.no_extra and not args.no_events
+    extra = args.full and world == 1 and not use_dist and not args.no_extra and not args.no_events
     if extra:
         nav.set_split(1)
         for _ in range(2):
@@ -772,7 +821,7 @@ def main():
                     pass
         if modes:
             out["other_modes"] = modes
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads, allowed, quota = host_threads()   # every core this process may use
             sample = args.cpu_sample or min(P, max(256, 4 * threads))
             out["cpu_baseline"] = cpu_baseline(frame, params, sample, threads)
@@ -815,6 +864,8 @@ def single_process(args):
     poses = np.concatenate([f.poses for f in frames])
     weights = np.full(P * n, 1.0 / (P * n))
 
+    events = args.full and not args.no_events
+
     def run(nav):
         nav.upload_state(planes, counts, poses, weights)
         nav.set_measurements(frames[0].z)
@@ -824,7 +875,7 @@ def single_process(args):
         for _ in range(PREROLL_STEPS + args.warmup):
             nav.step_async(0.5)
         nav.sync()
-        nav.timing_reset(max(1, min(args.events_every, 255)))
+        nav.timing_reset(max(1, min(args.events_every, 255)) if events else 0)
         t0 = time.perf_counter()
         for _ in range(args.steps):
             nav.step_async(0.5)
@@ -834,8 +885,10 @@ def single_process(args):
 
     nav = navigator.PHDNavigator(params, particlecount=P * n, devices=devices)
     elapsed, t_posted = run(nav)
+    if args.dump_outputs:
+        dump_outputs(nav, args.dump_outputs)
     rep = nav.multi_report()
-    kernels = nav.last_timings()
+    kernels = nav.last_timings() if events else {}
     resampled = bool(nav.resample_sources()[1])
     nav.close()
     out = {"metric": "PHD updates/sec (particles x components x measurements)", "value": P * n * Cc * M * args.steps / elapsed,
@@ -845,14 +898,15 @@ def single_process(args):
                                   "multi-device handle (phd_create_multi: a worker thread per shard, peer stores, plan on the device), devices %s"
                                   % (args.config, P, Cc, M, args.weights, devices),
                       "particles_per_gpu": P, "components": Cc, "measurements": M, "max_quantity": maxq,
-                      "parallelism": "particles sharded x%d in one process" % n},
-           "multi_host": {"post_us_per_step": rep["post_us"], "worker_issue_us_per_step": rep["issue_us"], "worker_hip_calls_us_per_step": rep["issue_calls_us"],
-                          "posting_all_steps_ms": t_posted * 1e3, "phase_ms_first_shard": rep["phase_ms"], "phase_samples": rep["sampled_steps"],
-                          "p2p": rep["p2p"], "resampled_every_step": resampled,
-                          "note": "post = the caller's thread inside phd_step_async (it only posts); worker issue = host time one shard's thread needs to issue "
-                                  "a step (launches, two events, 2 (n - 1) stream waits); phases = device time on the first shard's stream"},
-           "kernel_ms_first_shard": kernels}
-    if len(set(devices)) == 1:
+                      "parallelism": "particles sharded x%d in one process" % n}}
+    if events:   # (the phases are sampled with the kernel events; the host's diagnostics go with them)
+        out["multi_host"] = {"post_us_per_step": rep["post_us"], "worker_issue_us_per_step": rep["issue_us"], "worker_hip_calls_us_per_step": rep["issue_calls_us"],
+                             "posting_all_steps_ms": t_posted * 1e3, "phase_ms_first_shard": rep["phase_ms"], "phase_samples": rep["sampled_steps"],
+                             "p2p": rep["p2p"], "resampled_every_step": resampled,
+                             "note": "post = the caller's thread inside phd_step_async (it only posts); worker issue = host time one shard's thread needs to issue "
+                                     "a step (launches, two events, 2 (n - 1) stream waits); phases = device time on the first shard's stream"}
+        out["kernel_ms_first_shard"] = kernels
+    if args.full and len(set(devices)) == 1:
         p1 = prm3d_defaults(max_particles=P * n, max_components=maxq, max_measurements=M)
         p1.max_quantity = maxq
         one = navigator.PHDNavigator(p1, particlecount=P * n, device=devices[0])

@@ -4,8 +4,8 @@
 # Everything a verb writes goes under gpurun_out/<tag>/ (merged back by gpurun). Steps are joined so that nothing follows a
 # GPU step that timed out or failed.
 #   tests  <tag> [pytest -k expression]            the GPU suite (or the part -k selects), one process
-#   bench  <tag> [bench.py args...]                one bench line + a short summary of it
-#   quick  <tag> "<-k expr>" [stamp kernel ids...] tests selected by -k, the phase stamps of the kernels named, the default bench line
+#   bench  <tag> [bench.py args...]                one bench line + a short summary of it (add --full for the figures the summary prints)
+#   quick  <tag> "<-k expr>" [stamp kernel ids...] tests selected by -k, the phase stamps of the kernels named, the --full bench line
 #   so-ab  <tag> <cfg,cfg,...> <so> [<so>...]      A/B of library builds (files under monorfs_amd/csrc) on bench configs (B, S, A, Bsteady), two rounds
 #   env-ab <tag> <VAR> <a> <b> [-k expr]           A/B of an environment switch of the library on the default bench line
 #   stamps <tag> <frame> <kernel id> [...]         scripts/stamps.py (shader-clock phases per workgroup)
@@ -43,7 +43,7 @@ quick)
   echo "pytest rc=$rc" | tee -a $O/tests.log; tail -4 $O/tests.log; [ $rc -eq 0 ] || exit 1
   rm -f monorfs_amd/csrc/libphdhip_stamps*.so
   for k in "$@"; do timeout -k 10 300 python scripts/stamps.py survey $k 2>/dev/null | tail -2 | sed "s/^/kernel $k: /" | tee -a $O/stamps.log || exit 1; done
-  timeout -k 10 500 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; rc=$?; echo "bench rc=$rc"
+  timeout -k 10 500 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; rc=$?; echo "bench rc=$rc"
   [ $rc -eq 0 ] && summary $O/bench.json; exit $rc ;;
 so-ab)
   CFGS=${1:?configs}; shift
@@ -63,7 +63,7 @@ env-ab)
     echo "pytest ($VAR=$B) rc=$rc" | tee -a $O/tests.log; tail -3 $O/tests.log; [ $rc -eq 0 ] || exit 1
   fi
   for v in $A $B $A $B; do
-    env $VAR=$v timeout -k 10 500 python bench.py --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err || { echo "bench $VAR=$v failed"; exit 1; }
+    env $VAR=$v timeout -k 10 500 python bench.py --full --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err || { echo "bench $VAR=$v failed"; exit 1; }
     echo "$VAR=$v"; summary $O/bench_$v.json
   done ;;
 stamps)
@@ -75,12 +75,12 @@ prof)
 final)
   timeout -k 10 1100 python -m pytest tests -m gpu -q --durations=10 > $O/tests.log 2>&1; rc=$?
   echo "pytest rc=$rc" | tee -a $O/tests.log; tail -16 $O/tests.log; [ $rc -eq 0 ] || exit 1
-  timeout -k 10 500 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; exit 1; }
   summary $O/bench_default.json
   for w in steady survey; do
-    timeout -k 10 200 python bench.py --force-dist --weights $w --steps 40 --warmup 3 --no-cpu-baseline --no-extra > $O/forcedist_$w.json 2> $O/forcedist_$w.err || { echo "forcedist $w failed"; exit 1; }
+    timeout -k 10 200 python bench.py --full --force-dist --weights $w --steps 40 --warmup 3 --no-cpu-baseline --no-extra > $O/forcedist_$w.json 2> $O/forcedist_$w.err || { echo "forcedist $w failed"; exit 1; }
     echo "force-dist $w"; summary $O/forcedist_$w.json
-    timeout -k 10 200 python bench.py --weights $w --steps 40 --warmup 3 --no-cpu-baseline --no-extra > $O/plain_$w.json 2> $O/plain_$w.err || exit 1
+    timeout -k 10 200 python bench.py --full --weights $w --steps 40 --warmup 3 --no-cpu-baseline --no-extra > $O/plain_$w.json 2> $O/plain_$w.err || exit 1
     echo "plain $w"; summary $O/plain_$w.json
   done ;;
 *) echo "unknown verb $VERB"; exit 2 ;;
