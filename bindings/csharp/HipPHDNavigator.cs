@@ -48,6 +48,7 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_update_motion(HandleRef nav, IntPtr odometry6, IntPtr noise6, int nparticles, [MarshalAs(UnmanagedType.U1)] bool perfectstill);
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik_grad(HandleRef nav, IntPtr poses7, int nposes, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, IntPtr result, IntPtr gradients6);
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik(HandleRef nav, IntPtr poses7, int nposes, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, IntPtr result);
+	[DllImport(Lib)] public extern static int    phd_set_depth_map(HandleRef nav, IntPtr depth, int width, int height);
 	[DllImport(Lib)] public extern static int    phd_slam_update(HandleRef nav, IntPtr z3, int nmeasurements, [MarshalAs(UnmanagedType.U1)] bool onlymapping, double uresample);
 	[DllImport(Lib)] public extern static IntPtr phd_weights(HandleRef nav, out int length);
 	[DllImport(Lib)] public extern static int    phd_best_particle(HandleRef nav);
@@ -60,18 +61,19 @@ public class PhdHipLib
 /// PHD SLAM solver running PHDNavigator.SlamUpdate on the GPU. The motion model, its random
 /// generators and every per-particle object (TrackVehicle, trajectories) stay in managed code.
 /// </summary>
-public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRangeMeasurement>
+public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D, PixelRangeMeasurement>
+	where MeasurerT : PRM3DMeasurer, IMeasurer<MeasurerT, Pose3D, PixelRangeMeasurement>, new()
 {
-	HandleRef nav;
+	protected HandleRef nav;
 	public int ParticleCount { get; set; }
-	public TrackVehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement>[] VehicleParticles { get; private set; }
+	public TrackVehicle<MeasurerT, Pose3D, PixelRangeMeasurement>[] VehicleParticles { get; private set; }
 	public double[] VehicleWeights { get; private set; }
 	public int BestParticle { get; private set; }
 
 	/// <summary>gpus: how many GPUs of the node the particles are sharded over (devices 0 .. gpus - 1, one handle, this
 	/// thread: phd_create_multi); particlecount must then be a multiple of it. 1, or a mapping-only navigator (one particle):
 	/// a single-device handle.</summary>
-	public HipPHDNavigator(Vehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement> vehicle, int particlecount, bool onlymapping = false, int gpus = 1)
+	public HipPHDNavigatorCore(Vehicle<MeasurerT, Pose3D, PixelRangeMeasurement> vehicle, int particlecount, bool onlymapping = false, int gpus = 1)
 		: base(vehicle, onlymapping)
 	{
 		ParticleCount = particlecount;
@@ -89,6 +91,7 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 		p.merge_threshold = Config.MergeThreshold; p.exploration_threshold = Config.ExplorationThreshold;
 		p.density_distance_threshold = Config.DensityDistanceThreshold;
 		p.max_particles = particlecount; p.max_components = Math.Max(Config.MaxQuantity, 640); p.max_measurements = 256;
+		AdjustParams(ref p, vehicle);
 		int[] devices = new int[Math.Max(gpus, 1)];
 		for (int i = 0; i < devices.Length; i++) devices[i] = i;
 		IntPtr h = (gpus > 1 && !onlymapping) ? PhdHipLib.phd_create_multi(ref p, devices, devices.Length) : PhdHipLib.phd_create(ref p, 0);
@@ -97,25 +100,31 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 		reset(RefVehicle, new double[0], new double[0], new double[0], onlymapping ? 1 : particlecount);
 	}
 
-	Exception Fail(string message, int status)
+	/// <summary>The particles' measurer where it is not the explorer's (HipKinectPHDNavigator: the inflated film).</summary>
+	protected virtual void AdjustParams(ref PhdParams p, Vehicle<MeasurerT, Pose3D, PixelRangeMeasurement> vehicle) { }
+
+	/// <summary>Inputs of the coming step besides the measurements (HipKinectPHDNavigator: the depth frame).</summary>
+	protected virtual void BeforeSlamUpdate() { }
+
+	protected Exception Fail(string message, int status)
 	{
 		var e = new InvalidOperationException(message);
 		e.Data["module"] = (status == 3) ? "association" : "phdhip";     // Simulation.cs:662-670
 		return e;
 	}
 
-	void Check(int status)
+	protected void Check(int status)
 	{
 		if (status != 0) { throw Fail(Marshal.PtrToStringAnsi(PhdHipLib.phd_last_error(nav)), status); }
 	}
 
-	void reset(Vehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement> vehicle, double[] w, double[] mean, double[] cov, int particlecount)
+	void reset(Vehicle<MeasurerT, Pose3D, PixelRangeMeasurement> vehicle, double[] w, double[] mean, double[] cov, int particlecount)
 	{
 		double[] pose = vehicle.Pose.State;
 		fixed (double* pp = pose) fixed (double* pw = w) fixed (double* pm = mean) fixed (double* pc = cov) {
 			Check(PhdHipLib.phd_reset(nav, particlecount, (IntPtr) pp, (IntPtr) pw, (IntPtr) pm, (IntPtr) pc, w.Length));
 		}
-		VehicleParticles = new TrackVehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement>[particlecount];
+		VehicleParticles = new TrackVehicle<MeasurerT, Pose3D, PixelRangeMeasurement>[particlecount];
 		for (int i = 0; i < particlecount; i++) {
 			VehicleParticles[i] = vehicle.TrackClone(Config.MotionCovarianceMultiplier, Config.MeasurementCovarianceMultiplier,
 			                                         Config.NavigatorPD, Config.NavigatorClutterDensity, true);
@@ -125,7 +134,7 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 		BestParticle = 0;
 	}
 
-	public override TrackVehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement> BestEstimate { get { return VehicleParticles[BestParticle]; } }
+	public override TrackVehicle<MeasurerT, Pose3D, PixelRangeMeasurement> BestEstimate { get { return VehicleParticles[BestParticle]; } }
 
 	public override Map BestMapModel
 	{
@@ -171,7 +180,7 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 			v.CopyTo(noise, 6 * i);
 		}
 		fixed (double* pr = reading) fixed (double* pn = noise) {
-			Check(PhdHipLib.phd_update_motion(nav, (IntPtr) pr, OnlyMapping ? IntPtr.Zero : (IntPtr) pn, n, SimulatedVehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement>.PerfectStill));
+			Check(PhdHipLib.phd_update_motion(nav, (IntPtr) pr, OnlyMapping ? IntPtr.Zero : (IntPtr) pn, n, SimulatedVehicle<MeasurerT, Pose3D, PixelRangeMeasurement>.PerfectStill));
 		}
 		UpdateTrajectory(time);
 	}
@@ -217,6 +226,7 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 		double[] z = new double[3 * measurements.Count];
 		for (int i = 0; i < measurements.Count; i++) { measurements[i].ToLinear().CopyTo(z, 3 * i); }
 		double u = (double) Util.Uniform.Next();                           // PHDNavigator.cs:727: the RNG stays managed
+		BeforeSlamUpdate();
 		fixed (double* pz = z) { Check(PhdHipLib.phd_slam_update(nav, (IntPtr) pz, measurements.Count, OnlyMapping, u)); }
 
 		int n; bool resampled;
@@ -226,7 +236,7 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 		if (resampled) {                                                    // apply the device's choice to the managed particles
 			int[] sources = new int[n];
 			Marshal.Copy(src, sources, 0, n);
-			var particles = new TrackVehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement>[n];
+			var particles = new TrackVehicle<MeasurerT, Pose3D, PixelRangeMeasurement>[n];
 			for (int i = 0; i < n; i++) { particles[i] = RefVehicle.TrackClone(VehicleParticles[sources[i]], true); }   // :740
 			VehicleParticles = particles;
 		}
@@ -249,5 +259,49 @@ public unsafe class HipPHDNavigator : Navigator<PRM3DMeasurer, Pose3D, PixelRang
 	}
 
 	public override void Dispose() { if (nav.Handle != IntPtr.Zero) { PhdHipLib.phd_destroy(nav); nav = new HandleRef(this, IntPtr.Zero); } }
+}
+
+/// <summary>The PRM3D solver (Program.cs `-i` simulation / record inputs).</summary>
+public class HipPHDNavigator : HipPHDNavigatorCore<PRM3DMeasurer>
+{
+	public HipPHDNavigator(Vehicle<PRM3DMeasurer, Pose3D, PixelRangeMeasurement> vehicle, int particlecount, bool onlymapping = false, int gpus = 1)
+		: base(vehicle, particlecount, onlymapping, gpus) { }
+}
+
+/// <summary>
+/// The Kinect solver (Program.cs:197-204, `-i kinect`): the same body with KinectMeasurer's occlusion-aware detection
+/// probability (KinectMeasurer.cs:151-173), fed with the current depth frame before every step (phd_set_depth_map).
+/// Wiring: in Simulation.FromFiles, for VehicleType.Kinect with MeasurerT == KinectMeasurer, construct this class where the
+/// switch of Simulation.cs:352-379 constructs the navigator.
+/// </summary>
+public unsafe class HipKinectPHDNavigator : HipPHDNavigatorCore<KinectMeasurer>
+{
+	float[] frame = new float[0];
+
+	public HipKinectPHDNavigator(Vehicle<KinectMeasurer, Pose3D, PixelRangeMeasurement> vehicle, int particlecount, bool onlymapping = false, int gpus = 1)
+		: base(vehicle, particlecount, onlymapping, gpus) { }
+
+	/// <summary>KinectTrackVehicle (KinectTrackVehicle.cs:66-68): the particles' film is the explorer's inflated by -Border.</summary>
+	protected override void AdjustParams(ref PhdParams p, Vehicle<KinectMeasurer, Pose3D, PixelRangeMeasurement> vehicle)
+	{
+		int border = ((KinectVehicle) vehicle).Border;
+		p.measurer[3] += border; p.measurer[4] += border;           // Rectangle.Inflate(-Border, -Border)
+		p.measurer[5] -= 2 * border; p.measurer[6] -= 2 * border;
+	}
+
+	/// <summary>The particles' GetDepth() closure returns the current frame, float[ResX][ResY] indexed [x][y]; the library takes
+	/// it row-major, depth[y * ResX + x]. Values go as they are (no unit conversion: INTEGRATION.md, "Kinect input").</summary>
+	protected override void BeforeSlamUpdate()
+	{
+		float[][] depth = VehicleParticles[0].Measurer.GetDepth();
+		int w = depth.Length, h = (w > 0) ? depth[0].Length : 0;
+		if (w == 0 || h == 0) { Check(PhdHipLib.phd_set_depth_map(nav, IntPtr.Zero, 0, 0)); return; }
+		if (frame.Length != w * h) { frame = new float[w * h]; }
+		for (int x = 0; x < w; x++) {
+			float[] column = depth[x];
+			for (int y = 0; y < h; y++) { frame[y * w + x] = column[y]; }
+		}
+		fixed (float* pf = frame) { Check(PhdHipLib.phd_set_depth_map(nav, (IntPtr) pf, w, h)); }
+	}
 }
 }

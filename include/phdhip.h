@@ -41,7 +41,8 @@ extern "C" {
 #define PHD_API_VERSION 4   /* 2: phd_create_multi, phd_set_association_workspace; phd_migration_local_async gone
                                3: phd_multi_report; phd_device_local_weights is an export buffer; the migration plan is made on the device
                                4: the sharded step without a host wait (phd_step_global_device_async, phd_migration_push_async, the IPC
-                                  calls); phd_device_local_weights holds P + 1 doubles; the device keeps one 80-byte record per component */
+                                  calls); phd_device_local_weights holds P + 1 doubles; the device keeps one 80-byte record per component
+                               (4, added: phd_set_depth_map / phd_test_detection_probability, the Kinect model; hosts detect them by symbol) */
 
 /* status codes */
 #define PHD_OK                    0
@@ -185,6 +186,28 @@ int phd_slam_update(phd_navigator* nav, const double* z3, int nmeasurements,
  * on the handle, and a stream lent with phd_set_stream, take the fork / join order — INTEGRATION.md, "Posting steps back to
  * back").                                                                                         */
 int phd_set_measurements(phd_navigator* nav, const double* z3, int nmeasurements);
+/* Kinect input (KinectMeasurer.FuzzyVisibleM, KinectMeasurer.cs:151-173; PRM3D handles only, else PHD_ERR_BAD_ARGUMENT): the
+ * current depth frame, row-major depth[y * width + x] with width = ResX and height = ResY (the reference's float[ResX][ResY]
+ * depth[x][y], flattened), 1..PHD_DEPTH_MAX on each side. With a map, the detection probability of a pixel-range point
+ * z = (X, Y, range) — everywhere the step evaluates it: the sweep, the Kalman emit and SetLogLikeMatrix; NOT the quasi set
+ * log-likelihood (phd_quasi_set_loglik[_grad]), which keeps the constant pd as the reference does — is
+ *     base = the PRM3D visibility clamped to [0, 1];  0 if base == 0
+ *     x = (int) (X + (float) ResX / 2), y = (int) (Y + (float) ResY / 2)  (truncated; a pixel outside the image: 0)
+ *     d = depth[y * width + x]; 0 if d is NaN ("no reading")
+ *     r = (float) range;  m = min(base, (r - (float) rangemin) / ramp[2], (d - r) / ramp[2])  (float32 subtractions)
+ *     PD = max(0, min(1, m)) * pd
+ * Depth values are compared with the range as given, nothing is converted (units are the caller's); NaN and +-inf are
+ * accepted here — the one exception to the non-finite rule above. The map is sticky: every step posted after the call uses
+ * it until the next call; depth = NULL with 0 x 0 switches it off (exactly the PRM3D path again). The buffer is copied before
+ * the call returns (pinned staging, an asynchronous copy on the handle's stream ordered before the next step); a map larger
+ * than any before (re)allocates the device buffer, and that call waits for the handle's streams. A multi-device handle
+ * gives every shard the whole map. A refused call (bad arguments) leaves the previous map in place, and so does a failed
+ * allocation on a single-device handle.                                      */
+#define PHD_DEPTH_MAX 4096
+int phd_set_depth_map(phd_navigator* nav, const float* depth, int width, int height);
+/* Test surface of the above: the device's detection probability (the step's own __device__ function, with the handle's
+ * parameters and current map) at n pixel-range points z3[n][3] -> out[n]. Waits for the device.                        */
+int phd_test_detection_probability(phd_navigator* nav, const double* z3, int n, double* out);
 int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample);
 int phd_sync(phd_navigator* nav);
 /* Workspace of the set log-likelihood for data-association clusters of 65 .. 256 rows (MurtyPairing, GraphCombinatorics.cs:

@@ -75,6 +75,8 @@ def load():
         "phd_download_state_soa": (C.c_int, [P, C.c_int, dp, ip, dp, dp]),
         "phd_slam_update": (C.c_int, [P, dp, C.c_int, C.c_uint8, C.c_double]),
         "phd_set_measurements": (C.c_int, [P, dp, C.c_int]),
+        "phd_set_depth_map": (C.c_int, [P, C.POINTER(C.c_float), C.c_int, C.c_int]),
+        "phd_test_detection_probability": (C.c_int, [P, dp, C.c_int, dp]),
         "phd_step_async": (C.c_int, [P, C.c_uint8, C.c_double]),
         "phd_sync": (C.c_int, [P]),
         "phd_set_frozen": (C.c_int, [P, C.c_uint8]),
@@ -139,4 +141,4 @@ EXPORTS = ["phd_api_version", "phd_default_params", "phd_create", "phd_create_mu
            "phd_plan_migration", "phd_test_migration_plan", "phd_multi_report", "phd_last_resampled", "phd_migration_send_buffer", "phd_migration_recv_buffer", "phd_migration_pack_async",
            "phd_migration_unpack_async", "phd_device_gather_buffer", "phd_step_global_device_async", "phd_migration_ipc_export", "phd_migration_ipc_open",
            "phd_migration_set_peers", "phd_migration_recv_is_finegrained", "phd_migration_push_async", "phd_migration_set_landing", "phd_stream", "phd_set_stream", "phd_timing_reset", "phd_last_timings", "phd_last_timing_counts", "phd_upload_state_soa",
-           "phd_download_state_soa"]
+           "phd_download_state_soa", "phd_set_depth_map", "phd_test_detection_probability"]

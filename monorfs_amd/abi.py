@@ -60,6 +60,29 @@ def prm3d_defaults(max_particles=1, max_components=600, max_measurements=64):
     return p
 
 
+def kinect_defaults(max_particles=1, max_components=600, max_measurements=64, delta=4):
+    """The measurer of a KinectTrackVehicle particle: the PRM3D defaults with KinectVehicle's camera at a frame decimation
+    `delta` (KinectDelta). Focal 575.8156 / delta; film Rectangle(-640/delta/2, -480/delta/2, 640/delta, 480/delta) with C#
+    integer division (KinectVehicle.cs:220-224, 261-266), inflated by -Border, Border = 27 (KinectTrackVehicle.cs:66-68);
+    range clip [0.1f, 4f]. Returns (params, (resx, resy)): the depth frame phd_set_depth_map takes is resy rows of resx."""
+    import numpy as np
+    delta = int(delta)
+    if delta < 1:
+        raise ValueError("delta >= 1")
+
+    def cdiv(a, b):   # C# integer division truncates toward zero
+        q = abs(a) // abs(b)
+        return q if (a >= 0) == (b >= 0) else -q
+
+    resx, resy = cdiv(640, delta), cdiv(480, delta)
+    border = 27
+    x, y, w, h = cdiv(-resx, 2), cdiv(-resy, 2), resx, resy   # Rectangle(-ResX / 2, -ResY / 2, ResX, ResY)
+    x, y, w, h = x + border, y + border, w - 2 * border, h - 2 * border   # Rectangle.Inflate(-Border, -Border)
+    p = prm3d_defaults(max_particles, max_components, max_measurements)
+    p.measurer[:] = [575.8156 / delta, float(np.float32(0.1)), float(np.float32(4.0)), x, y, w, h]
+    return p, (resx, resy)
+
+
 def params_from_dict(d, **caps):
     """Build a parameter block from the `params` object of a golden fixture."""
     p = PhdParams()

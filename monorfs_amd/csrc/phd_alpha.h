@@ -764,7 +764,7 @@ __host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap)
 // which then run BESIDE the association below instead of behind it; *helper_go says whether it did.
 __device__ __forceinline__ unsigned int my_xcd() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u; }   // HW_REG_XCC_ID
 
-template <int ZB, bool QUASI, bool GRAD = false, int TAG = 0, int DEFER = 0>
+template <int ZB, bool QUASI, bool GRAD = false, int TAG = 0, int DEFER = 0, bool DEPTH = false>
 __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const StepBufs& a, int ncap, double* smem, double* gws = nullptr, int pin = -1,
                                                  int* helper_go = nullptr)
 {
@@ -1057,8 +1057,9 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		for (int j = tid; j < J; j += 256) {
 			double m[3] = {lm[j], lm[JS + j], lm[2 * JS + j]}, z[3], l[3];
 			measure_perfect(prm, pose, m, z, l);
+			const float dz = (!QUASI && DEPTH) ? depth_at(prm, z) : 0.0f;   // (the quasi set log-likelihood keeps the constant PD, :574-575)
 			zh[j] = z[0]; zh[JS + j] = z[1]; zh[2 * JS + j] = z[2];
-			const double pdv = QUASI ? prm.pd : detection_probability_m(prm, z);
+			const double pdv = QUASI ? prm.pd : detection_probability_m<!QUASI && DEPTH>(prm, z, dz);
 			lpd[j] = log(pdv);
 			lmd[j] = log(1 - pdv);
 #pragma unroll
@@ -1995,22 +1996,22 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 #ifndef PHD_ASSOC_WAVES
 #define PHD_ASSOC_WAVES 4
 #endif
-template <int ZB>
+template <int ZB, bool DEPTH = false>
 __global__ __launch_bounds__(256, PHD_ASSOC_WAVES) void k_alpha_assoc(const DevParams prm, const StepBufs a, int ncap)
 {
 	extern __shared__ __align__(16) double smem[];
 	PHD_TL_BEGIN;
 	PHD_SET_PRIO(PHD_LAT_PRIO);
-	alpha_assoc_body<ZB, false>(prm, a, ncap, smem);
+	alpha_assoc_body<ZB, false, false, 0, 0, DEPTH>(prm, a, ncap, smem);
 	PHD_TL_END(3);
 }
 
 // the same with the particles that need the ordered replay (a cluster of more than 5 rows) left to k_alpha_big
-template <int ZB>
+template <int ZB, bool DEPTH = false>
 __global__ __launch_bounds__(256, PHD_ASSOC_WAVES) void k_alpha_assoc_main(const DevParams prm, const StepBufs a, int ncap)
 {
 	extern __shared__ __align__(16) double smem[];
-	alpha_assoc_body<ZB, false, false, 2, 1>(prm, a, ncap, smem);
+	alpha_assoc_body<ZB, false, false, 2, 1, DEPTH>(prm, a, ncap, smem);
 }
 
 // WeightAlpha's last line for every particle (PHDNavigator.cs:390-392, :335), when k_alpha_density left it open (a.defer):
@@ -2309,14 +2310,14 @@ __global__ __launch_bounds__(256, PHD_DENS_WAVES) void k_alpha_density(const Dev
 // k_alpha_density's. A replay is one wave deep in the solver for hundreds of microseconds: started first, beside a launch
 // that fills the machine for as long, it costs the step nothing. (On a stream of its own it did not overlap: HIP's streams
 // share four hardware queues, and with more of those the whole step ran a fifth slower.)
-template <int ZB>
+template <int ZB, bool DEPTH = false>
 __global__ __launch_bounds__(256, 4) void k_alpha_density_big(const DevParams prm, const StepBufs a, int ncap, int nbig)
 {
 	extern __shared__ __align__(16) double smem[];
 	if ((int) blockIdx.x < nbig) {
 		const int n = a.biglist[0];
 		for (int w = blockIdx.x; w < n; w += nbig) {
-			alpha_assoc_body<ZB, false, false, 0, 2>(prm, a, ncap, smem, nullptr, a.biglist[1 + w]);
+			alpha_assoc_body<ZB, false, false, 0, 2, DEPTH>(prm, a, ncap, smem, nullptr, a.biglist[1 + w]);
 			__syncthreads();   // (the next particle reuses the LDS arrays)
 		}
 		return;

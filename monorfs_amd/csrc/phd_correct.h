@@ -51,7 +51,7 @@ __device__ __forceinline__ void load_predicted(const DevParams& prm, const StepB
 // SPREAD (the one-launch chain: one workgroup per CU, one wave per SIMD): the runs are dealt to the four waves in turn, so that all
 // four SIMDs work on a short list; on a full machine a wave takes 64 neighbouring runs (fewest wave-passes through the Kalman path:
 // the SIMDs are shared with three other workgroups in the same phase).
-template <bool LEAN = false, bool SPREAD = false>
+template <bool LEAN = false, bool SPREAD = false, bool DEPTH = false>
 __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const StepBufs& a, double* pool)
 {
 	double* const etab = pool;
@@ -99,10 +99,13 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 		double w, m[3], P[6];
 		load_predicted(prm, a, vin, p, n, c, w, m, P);
 		double zh[3], H[9], PH[9], Sinv[9], qmult, pdw;
+		float dz = 0.0f;
 		{
 			double l[3];
 			measure_perfect(prm, pose, m, zh, l);
-			pdw = detection_probability_m(prm, zh) * w;
+			// (with a depth map only the pixel's load goes here; the detection probability follows S, under which its latency runs)
+			if (DEPTH) dz = depth_at(prm, zh);
+			else pdw = detection_probability_m(prm, zh) * w;
 			// (the rotation matrix is made HERE, per run, from the quaternion in scalar registers: ~20 instructions against nine
 			// doubles kept — spilled, in the fused launch — across everything else; the empty asm keeps the compiler from hoisting it)
 			PoseD pq = pose;
@@ -139,6 +142,7 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 			inv_gen3(S, Sinv, det);
 			qmult = PHD_INV_2PI / sqrt(fabs(det));
 		}
+		if (DEPTH) pdw = detection_probability_m<true>(prm, zh, dz) * w;
 		// K = P H^T S^-1 (:895), P' = (I - K H) P (:897): the component's, whatever the measurement
 		double K[9], Pn[6];
 #pragma unroll
@@ -312,8 +316,9 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 #ifndef PHD_EF_WAVES
 #define PHD_EF_WAVES 3   // waves per SIMD the register allocation of k_emit_finish aims at (tuning: scripts/ab_variants.sh)
 #endif
+template <bool DEPTH = false>
 __global__ __launch_bounds__(256, PHD_EF_WAVES) void k_emit_finish(const DevParams prm, const StepBufs a)
 {
 	__shared__ __align__(16) double pool[EMIT_LDS_DOUBLES];
-	emit_finish_body(prm, a, pool);
+	emit_finish_body<false, false, DEPTH>(prm, a, pool);
 }

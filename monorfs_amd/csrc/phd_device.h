@@ -75,6 +75,12 @@ struct DevParams {
 	                        // coordinate is always 0, its row of H is 0 and R gets a 1 there, so S, its determinant, K and
 	                        // every quadratic form are those of the 2-D model (the multiplier exponent is -1 in both, Gaussian.cs:155)
 	double lin_range;       // Linear2DMeasurer.Range: the visible square [-range, range]^2
+	// KinectMeasurer's depth frame (phd_set_depth_map; KinectMeasurer.cs:151-173): row-major [depth_h][depth_w] float32 on the
+	// device, nullptr when no map is set (then every body runs exactly the PRM3D path). depth_hx / depth_hy are ResX / 2 and
+	// ResY / 2 as the reference computes them (float division, widened).
+	const float* depth;
+	int    depth_w, depth_h;
+	double depth_hx, depth_hy;
 };
 
 #define PHD_INV_2PI 0.15915494309189535   // Math.Pow(2 * Math.PI, -3 / 2) with C# integer division (Gaussian.cs:155)
@@ -165,8 +171,39 @@ __device__ __forceinline__ void measure_perfect(const DevParams& prm, const Pose
 	zh[1] = prm.focal * l[1] / l[2];
 }
 
-// FuzzyVisibleM (PRM3DMeasurer.cs:277-291) * detectionProbability (SimulatedVehicle.cs:335-338)
-__device__ __forceinline__ double detection_probability_m(const DevParams& prm, const double z[3])
+// The depth map's reading at the pixel of a pixel-range point (KinectMeasurer.cs:153-154, 163): x = (int) (X + ResX / 2),
+// y = (int) (Y + ResY / 2), truncated toward zero. The range is checked in double before the conversion; a pixel outside the
+// image reads -inf, which makes the occlusion term -inf and the detection probability 0 (the reference would throw there). The
+// load itself is unconditional (pixel 0 stands in for an outside point) so that a body can issue it as soon as h(m) is known
+// and let its latency run under the arithmetic that follows. Only with a map set (prm.depth != nullptr).
+__device__ __forceinline__ float depth_at(const DevParams& prm, const double z[3])
+{
+	PHD_REF_ARITH
+	const double xd = z[0] + prm.depth_hx, yd = z[1] + prm.depth_hy;
+	const bool in = xd > -1.0 && xd < (double) prm.depth_w && yd > -1.0 && yd < (double) prm.depth_h;
+	const int idx = in ? (int) yd * prm.depth_w + (int) xd : 0;
+	const float d = prm.depth[idx];
+	return in ? d : -INFINITY;
+}
+
+// KinectMeasurer.FuzzyVisibleM (KinectMeasurer.cs:151-173) on top of the PRM3D value `base` (already clamped to [0, 1]), with
+// the depth `d` that depth_at read: 0 where base is 0 or there is no reading (NaN); else the smaller of base, the float32 range
+// term (range - RangeClip.Min) and the occlusion term (depth - range), both over the double VisibilityRamp[2], clamped.
+__device__ __forceinline__ double kinect_visible(const DevParams& prm, const double z[3], double base, float d)
+{
+	PHD_REF_ARITH
+	if (base == 0.0 || isnan(d)) return 0.0;
+	const float r = (float) z[2];
+	double m = fmin(base, (double) (r - (float) prm.rmin) / prm.ramp[2]);
+	m = fmin(m, (double) (d - r) / prm.ramp[2]);
+	return fmax(0.0, fmin(1.0, m));
+}
+
+// FuzzyVisibleM (PRM3DMeasurer.cs:277-291) * detectionProbability (SimulatedVehicle.cs:335-338); DEPTH (the kernels launched
+// while a depth map is set): Kinect's, with `d` = depth_at at the same point, read by the caller as early as it can. The bodies
+// are compiled both ways so that the map costs the PRM3D path neither a branch nor a register.
+template <bool DEPTH = false>
+__device__ __forceinline__ double detection_probability_m(const DevParams& prm, const double z[3], float d = 0.0f)
 {
 	PHD_REF_ARITH
 	if (prm.linear2d) {   // Linear2DMeasurer.FuzzyVisibleM (Linear2DMeasurer.cs:151-162)
@@ -181,7 +218,9 @@ __device__ __forceinline__ double detection_probability_m(const DevParams& prm, 
 	double mind = fmin(z[0] - prm.left, prm.right - z[0]) / prm.ramp[0];
 	mind = fmin(mind, fmin(z[1] - prm.top, prm.bottom - z[1]) / prm.ramp[1]);
 	mind = fmin(mind, fmin(z[2] - prm.rmin, prm.rmax - z[2]) / prm.ramp[2]);
-	return fmax(0.0, fmin(1.0, mind)) * prm.pd;
+	double v = fmax(0.0, fmin(1.0, mind));
+	if (DEPTH) v = kinect_visible(prm, z, v, d);
+	return v * prm.pd;
 }
 
 // MeasurementJacobianL (PRM3DMeasurer.cs:157-177): H = Jproj(local) * R(q*)
@@ -353,12 +392,14 @@ struct CompMeas {
 	double pd;        // detection probability of the component
 };
 
+template <bool DEPTH = false>
 __device__ __forceinline__ void comp_measure(const DevParams& prm, const PoseD& pose, const double rq[9],
                                              const double m[3], const double P[6], CompMeas& o)
 {
 	PHD_REF_ARITH
 	double l[3];
 	measure_perfect(prm, pose, m, o.zh, l);
+	const float dz = DEPTH ? depth_at(prm, o.zh) : 0.0f;   // (its latency runs under the Jacobian and S)
 	jacobian_l(prm, l, rq, o.H);
 	const double Pf[9] = {P[0], P[1], P[2], P[1], P[3], P[4], P[2], P[4], P[5]};
 #pragma unroll
@@ -389,7 +430,7 @@ __device__ __forceinline__ void comp_measure(const DevParams& prm, const PoseD& 
 	double det;
 	inv_gen3(S, o.Sinv, det);
 	o.qmult = PHD_INV_2PI / sqrt(fabs(det));
-	o.pd    = detection_probability_m(prm, o.zh);
+	o.pd    = detection_probability_m<DEPTH>(prm, o.zh, dz);
 }
 
 // Kalman update of one (component, measurement) pair (PHDNavigator.cs:895-897):

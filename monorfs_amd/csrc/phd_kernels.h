@@ -300,7 +300,7 @@ __host__ __device__ inline int chain_lds_bytes(int cutcap)
 	return b;
 }
 
-template <int ZB, bool HALF = false>
+template <int ZB, bool HALF = false, bool DEPTH = false>
 __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, const StepBufs a, int cutcap, int with_alpha)
 {
 	extern __shared__ __align__(16) double smem[];
@@ -366,10 +366,10 @@ __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, 
 	else {
 	PHD_STAMP_DECL;
 	PHD_STAMP(0);
-	sweep_body<ZB, HALF>(prm, a, smem);
+	sweep_body<ZB, HALF, DEPTH>(prm, a, smem);
 	__syncthreads();   // (workgroup scope: the global writes of the step before are visible to this workgroup's loads)
 	PHD_STAMP(1);
-	emit_finish_body<false, true>(prm, a, smem);
+	emit_finish_body<false, true, DEPTH>(prm, a, smem);
 	__syncthreads();
 	PHD_STAMP(2);
 	prune_merge_body(prm, a, cutcap, smem);
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, 
 		if (threadIdx.x == 0) s_hgo = 0;
 		__syncthreads();
 		PHD_STAMP(3);
-		alpha_assoc_body<ZB, false, false, 1>(prm, a, cutcap, smem, nullptr, -1, a.dsplit ? &s_hgo : nullptr);
+		alpha_assoc_body<ZB, false, false, 1, 0, DEPTH>(prm, a, cutcap, smem, nullptr, -1, a.dsplit ? &s_hgo : nullptr);
 		__syncthreads();
 		PHD_STAMP(4);
 		if (!s_hgo) alpha_density_body(prm, a, smem);
@@ -430,13 +430,13 @@ __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, 
 // of the chain above at k_sweep's own register budget (four workgroups per CU), k_alpha_assoc and k_alpha_density behind it as
 // launches of their own (compiled into one kernel with the others they cost occupancy: 245 registers). The workgroups of a CU
 // drift apart — some in the dense pair loops, some in the latency-bound prune — and two launch boundaries go.
-template <int ZB, bool HALF = false>
+template <int ZB, bool HALF = false, bool DEPTH = false>
 __global__ __launch_bounds__(256, 4) void k_sweep_emit_prune(const DevParams prm, const StepBufs a, int cutcap)
 {
 	extern __shared__ __align__(16) double smem[];
-	sweep_body<ZB, HALF>(prm, a, smem);
+	sweep_body<ZB, HALF, DEPTH>(prm, a, smem);
 	__syncthreads();
-	emit_finish_body(prm, a, smem);
+	emit_finish_body<false, false, DEPTH>(prm, a, smem);
 	__syncthreads();
 	prune_merge_body(prm, a, cutcap, smem);
 }
@@ -1191,5 +1191,15 @@ __global__ __launch_bounds__(256) void k_finish_sharded(const StepBufs a, const 
 		slots[i] = slot;
 		if (!frozen) inslot[i] = slot;
 	}
+}
+
+// phd_test_detection_probability: detection_probability_m — the function the step's three call sites evaluate — on n
+// pixel-range points, with the handle's parameters and current depth map
+__global__ __launch_bounds__(256) void k_test_detection_probability(const DevParams prm, const double* __restrict__ z3, int n, double* __restrict__ out)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const double z[3] = {z3[(size_t) i * 3], z3[(size_t) i * 3 + 1], z3[(size_t) i * 3 + 2]};
+	out[i] = prm.depth ? detection_probability_m<true>(prm, z, depth_at(prm, z)) : detection_probability_m(prm, z);
 }
 #endif   // PHD_ONLY_EP

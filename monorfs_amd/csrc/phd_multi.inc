@@ -487,6 +487,19 @@ int multi_set_measurements(phd_navigator* nav, const double* z3, int nmeasuremen
 	return PHD_OK;
 }
 
+// every shard gets the whole map (each evaluates its own particles' components against it)
+int multi_set_depth_map(phd_navigator* nav, const float* depth, int width, int height)
+{
+	MultiState* m = nav->multi;
+	int rc = multi_enter(nav);
+	if (rc) return rc;
+	for (size_t s = 0; s < m->sh.size(); s++) {
+		rc = phd_set_depth_map(m->sh[s], depth, width, height);
+		if (rc) return multi_fail_from(nav, m->sh[s], rc, (int) s);
+	}
+	return PHD_OK;
+}
+
 int multi_forward_int(phd_navigator* nav, int what, long long value)
 {
 	MultiState* m = nav->multi;

@@ -42,7 +42,7 @@ struct SweepLds {
 // HALF (with ZB = 1, at most 32 measurements — the common frame of the reference's own scenes): lanes 32-63 hold the
 // measurements of lanes 0-31 again and take the component four further on, so a visit of the pair loop covers two
 // components and the loop is half as long; the two halves' partial sums of a measurement meet in the reductions.
-template <int ZB, bool HALF = false>
+template <int ZB, bool HALF = false, bool DEPTH = false>
 __device__ __forceinline__ void sweep_body(const DevParams& prm, const StepBufs& a, double* pool)
 {
 	static_assert(!HALF || ZB == 1, "HALF is a layout of the one-block kernel");
@@ -205,7 +205,7 @@ __device__ __forceinline__ void sweep_body(const DevParams& prm, const StepBufs&
 					CompMeas q;
 					double rq[9];
 					rotation(rq);
-					comp_measure(prm, pose, rq, m, P, q);
+					comp_measure<DEPTH>(prm, pose, rq, m, P, q);
 					tt[0] = q.zh[0]; tt[1] = q.zh[1]; tt[2] = q.zh[2];
 					tt[3] = -0.5 * q.Sinv[0];
 					tt[4] = -0.5 * (q.Sinv[1] + q.Sinv[3]);
@@ -368,7 +368,7 @@ __device__ __forceinline__ void sweep_body(const DevParams& prm, const StepBufs&
 				CompMeas q;
 				double rq[9];
 				rotation(rq);
-				comp_measure(prm, pose, rq, m, prm.birthP, q);
+				comp_measure<DEPTH>(prm, pose, rq, m, prm.birthP, q);
 				double* tt = tile + bi * 13;
 				tt[0] = q.zh[0]; tt[1] = q.zh[1]; tt[2] = q.zh[2];
 				tt[3] = -0.5 * q.Sinv[0];
@@ -435,7 +435,7 @@ __device__ __forceinline__ void sweep_body(const DevParams& prm, const StepBufs&
 #define PHD_SWEEP_WAVES 4
 #endif
 // (four measurement blocks per lane need 220 registers: two waves per SIMD is what that kernel gets, and what it asks for)
-template <int ZB, bool HALF = false>
+template <int ZB, bool HALF = false, bool DEPTH = false>
 #ifndef PHD_SWEEP2_WAVES
 #define PHD_SWEEP2_WAVES PHD_SWEEP_WAVES   // ... of the two-block kernel (65 - 128 measurements)
 #endif
@@ -444,6 +444,6 @@ __global__ __launch_bounds__(256, (ZB == 4 ? 2 : (ZB == 2 ? PHD_SWEEP2_WAVES : P
 	__shared__ __align__(16) double pool[SweepLds<ZB>::doubles];
 	PHD_TL_BEGIN;
 	PHD_SET_PRIO(PHD_DENSE_PRIO);
-	sweep_body<ZB, HALF>(prm, a, pool);
+	sweep_body<ZB, HALF, DEPTH>(prm, a, pool);
 	PHD_TL_END(6);
 }

@@ -125,6 +125,11 @@ struct phd_navigator {
 	// an event recorded behind the copy that reads it.
 	double* h_stage[2] = {nullptr, nullptr}; hipEvent_t ev_stage[2] = {nullptr, nullptr}; bool stage_used[2] = {false, false};
 	int stage_i = 0; size_t stagecap = 0;
+	// the depth map of phd_set_depth_map (KinectMeasurer): the device copy dp.depth points at (depthcap floats, grown on demand) and
+	// its own pair of pinned staging slots, guarded like h_stage (hdepthcap floats each)
+	float* d_depth = nullptr; size_t depthcap = 0;
+	float* h_depth[2] = {nullptr, nullptr}; hipEvent_t ev_depth[2] = {nullptr, nullptr}; bool depth_used[2] = {false, false};
+	int depth_i = 0; size_t hdepthcap = 0;
 	int nr_static_lds = 0;                           // static LDS of k_normalise_resample
 	// the step over a grid of workgroups (k_nr_*, phd_resample.h) for weight vectors of nr_grid_min .. 65 536 entries (environment
 	// PHD_NR_GRID_MIN; 0: never): its scratch, made on first use
@@ -256,6 +261,7 @@ DevParams make_dev_params(const phd_params& p)
 	d.emit_log_floor = (floor > 0) ? std::log(floor) : -INFINITY;
 	d.gate_metric = p.gate_metric;
 	d.maxq        = p.max_quantity;
+	d.depth = nullptr; d.depth_w = 0; d.depth_h = 0; d.depth_hx = 0; d.depth_hy = 0;   // no depth map: phd_set_depth_map
 	return d;
 }
 
@@ -377,7 +383,7 @@ const char* T_CH = "k_particle_chain";
 // latency-bound kernels of one sub-range overlap the arithmetic-bound kernels of another.
 // `pipe` >= 0 (phd_step_async, two sub-ranges): no fork and no join here — the caller has ordered the streams and ends the step on
 // the stream that finishes last, `pipe` (0 `stream`, 1 aux[0]); the other one's chain is enqueued first.
-template <int ZB>
+template <int ZB, bool DEPTH>
 int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, int pipe = -1)
 {
 	const int P = nav->P;
@@ -403,8 +409,8 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 		}
 		const int G = helpers ? 2 * P : P;
 		// (up to 32 measurements: the sweep with two components per visit, phd_sweep.h HALF)
-		if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_particle_chain<1, true>), dim3(G), dim3(256), (size_t) chain_lds_bytes<1>(nav->cutcap), nav->stream, nav->dp, bc, nav->cutcap, with_alpha ? 1 : 0);
-		else hipLaunchKernelGGL(k_particle_chain<ZB>, dim3(G), dim3(256), (size_t) chain_lds_bytes<ZB>(nav->cutcap), nav->stream, nav->dp, bc, nav->cutcap, with_alpha ? 1 : 0);
+		if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_particle_chain<1, true, DEPTH>), dim3(G), dim3(256), (size_t) chain_lds_bytes<1>(nav->cutcap), nav->stream, nav->dp, bc, nav->cutcap, with_alpha ? 1 : 0);
+		else hipLaunchKernelGGL((k_particle_chain<ZB, false, DEPTH>), dim3(G), dim3(256), (size_t) chain_lds_bytes<ZB>(nav->cutcap), nav->stream, nav->dp, bc, nav->cutcap, with_alpha ? 1 : 0);
 		timer_end(nav, T_CH);
 		HC(hipGetLastError());
 		nav->last_defer = 0;
@@ -430,25 +436,25 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 		if (nav->fuse_sep) {
 			const size_t ld3 = std::max(std::max(lp, (size_t) EMIT_LDS_DOUBLES * 8), (size_t) SweepLds<ZB>::doubles * 8);
 			timer_begin(nav, T_SEP, st);
-			if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_sweep_emit_prune<1, true>), dim3(n), dim3(256), ld3, st, nav->dp, b, nav->cutcap);
-			else hipLaunchKernelGGL(k_sweep_emit_prune<ZB>, dim3(n), dim3(256), ld3, st, nav->dp, b, nav->cutcap);
+			if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_sweep_emit_prune<1, true, DEPTH>), dim3(n), dim3(256), ld3, st, nav->dp, b, nav->cutcap);
+			else hipLaunchKernelGGL((k_sweep_emit_prune<ZB, false, DEPTH>), dim3(n), dim3(256), ld3, st, nav->dp, b, nav->cutcap);
 			timer_end(nav, T_SEP, st);
 		}
 		else
 #endif
 		{
 		timer_begin(nav, T_SW, st);
-		if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_sweep<1, true>), dim3(n), dim3(256), 0, st, nav->dp, b);
-		else hipLaunchKernelGGL(k_sweep<ZB>, dim3(n), dim3(256), 0, st, nav->dp, b);
+		if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_sweep<1, true, DEPTH>), dim3(n), dim3(256), 0, st, nav->dp, b);
+		else hipLaunchKernelGGL((k_sweep<ZB, false, DEPTH>), dim3(n), dim3(256), 0, st, nav->dp, b);
 		timer_end(nav, T_SW, st);
 		if (nav->fuse_ep < 0 ? ZB == 1 : nav->fuse_ep != 0) {
 			timer_begin(nav, T_EP, st, true);
-			hipLaunchKernelGGL(k_emit_prune, dim3(n), dim3(256), std::max(lp, (size_t) EMIT_LDS_DOUBLES * 8), st, nav->dp, b, nav->cutcap);
+			hipLaunchKernelGGL(k_emit_prune<DEPTH>, dim3(n), dim3(256), std::max(lp, (size_t) EMIT_LDS_DOUBLES * 8), st, nav->dp, b, nav->cutcap);
 			timer_end(nav, T_EP, st);
 		}
 		else {
 			timer_begin(nav, T_EF, st, true);
-			hipLaunchKernelGGL(k_emit_finish, dim3(n), dim3(256), 0, st, nav->dp, b);
+			hipLaunchKernelGGL(k_emit_finish<DEPTH>, dim3(n), dim3(256), 0, st, nav->dp, b);
 			timer_end(nav, T_EF, st);
 			timer_begin(nav, T_PM, st, true);
 			hipLaunchKernelGGL(k_prune_merge, dim3(n), dim3(256), lp, st, nav->dp, b, nav->cutcap);
@@ -457,17 +463,17 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 		}
 		if (with_alpha && defer) {
 			timer_begin(nav, T_WA, st, true);
-			hipLaunchKernelGGL(k_alpha_assoc_main<ZB>, dim3(n), dim3(256), lay.bytes, st, nav->dp, b, nav->cutcap);
+			hipLaunchKernelGGL((k_alpha_assoc_main<ZB, DEPTH>), dim3(n), dim3(256), lay.bytes, st, nav->dp, b, nav->cutcap);
 			timer_end(nav, T_WA, st);
 			// the particles it listed are worked off by the first workgroups of the densities' launch
 			const int nbig = std::max(1, std::min(nav->nbig, n));
 			timer_begin(nav, T_WD, st, true);
-			hipLaunchKernelGGL(k_alpha_density_big<ZB>, dim3(n + nbig), dim3(256), ldb, st, nav->dp, b, nav->cutcap, nbig);
+			hipLaunchKernelGGL((k_alpha_density_big<ZB, DEPTH>), dim3(n + nbig), dim3(256), ldb, st, nav->dp, b, nav->cutcap, nbig);
 			timer_end(nav, T_WD, st);
 		}
 		else if (with_alpha) {
 			timer_begin(nav, T_WA, st, true);
-			hipLaunchKernelGGL(k_alpha_assoc<ZB>, dim3(n), dim3(256), lay.bytes, st, nav->dp, b, nav->cutcap);
+			hipLaunchKernelGGL((k_alpha_assoc<ZB, DEPTH>), dim3(n), dim3(256), lay.bytes, st, nav->dp, b, nav->cutcap);
 			timer_end(nav, T_WA, st);
 			timer_begin(nav, T_WD, st, true);
 			hipLaunchKernelGGL(k_alpha_density, dim3(n), dim3(256), 0, st, nav->dp, b);
@@ -500,10 +506,18 @@ int launch_quasi(phd_navigator* nav, const StepBufs& b, int nposes, bool gradien
 
 int launch_map(phd_navigator* nav, const StepBufs& b, bool with_alpha, int pipe = -1)
 {
+	// (a depth map set: the kernels compiled with the Kinect detection probability, phd_device.h)
+	if (nav->dp.depth) {
+		switch (zb_of(nav->M)) {
+		case 1:  return launch_map_kernels<1, true>(nav, b, with_alpha, pipe);
+		case 2:  return launch_map_kernels<2, true>(nav, b, with_alpha, pipe);
+		default: return launch_map_kernels<4, true>(nav, b, with_alpha, pipe);
+		}
+	}
 	switch (zb_of(nav->M)) {
-	case 1:  return launch_map_kernels<1>(nav, b, with_alpha, pipe);
-	case 2:  return launch_map_kernels<2>(nav, b, with_alpha, pipe);
-	default: return launch_map_kernels<4>(nav, b, with_alpha, pipe);
+	case 1:  return launch_map_kernels<1, false>(nav, b, with_alpha, pipe);
+	case 2:  return launch_map_kernels<2, false>(nav, b, with_alpha, pipe);
+	default: return launch_map_kernels<4, false>(nav, b, with_alpha, pipe);
 	}
 }
 
@@ -697,6 +711,7 @@ int multi_set_map(phd_navigator* nav, int particle, const double* w, const doubl
 int multi_upload(phd_navigator* nav, int nparticles, int stride, const double* planes, const int32_t* counts, const double* poses7, const double* weights);
 int multi_download(phd_navigator* nav, int stride, double* planes, int32_t* counts, double* poses7, double* weights);
 int multi_set_measurements(phd_navigator* nav, const double* z3, int nmeasurements);
+int multi_set_depth_map(phd_navigator* nav, const float* depth, int width, int height);
 int multi_step(phd_navigator* nav, uint8_t onlymapping, double u_resample);
 int multi_sync(phd_navigator* nav);
 int multi_forward_int(phd_navigator* nav, int what, long long value);
@@ -885,7 +900,7 @@ phd_navigator* phd_create(const phd_params* params, int device)
 		// dynamic LDS limits, set when a handle is created: they depend on the handle's capacities only. The attribute belongs
 		// to the function ON THE CURRENT DEVICE, and the same kernels serve every handle of the process there: per device
 		// the limit is only ever raised.
-		struct DevLimits { int prune = 0, alpha[3] = {0, 0, 0}, chain[4] = {0, 0, 0, 0}; };
+		struct DevLimits { int prune = 0, alpha[3] = {0, 0, 0}, chain[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
 		static DevLimits limits[PHD_MAX_DEVICES];
 		static std::mutex limits_mu;   // (handles may be created from several host threads, one per GPU)
 		std::lock_guard<std::mutex> limits_guard(limits_mu);
@@ -893,37 +908,51 @@ phd_navigator* phd_create(const phd_params* params, int device)
 		const int lp = prune_lds(nav->cutcap).bytes;
 		if (lp > lim.prune) {
 			ok = ok && hipFuncSetAttribute((const void*) k_prune_merge, hipFuncAttributeMaxDynamicSharedMemorySize, lp) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_emit_prune, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lp, (int) (EMIT_LDS_DOUBLES * 8))) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_emit_prune<false>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lp, (int) (EMIT_LDS_DOUBLES * 8))) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_emit_prune<true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lp, (int) (EMIT_LDS_DOUBLES * 8))) == hipSuccess;
 #ifdef PHD_WITH_FUSE_SEP
 			const int l3[3] = {std::max(lp, (int) (SweepLds<1>::doubles * 8)), std::max(lp, (int) (SweepLds<2>::doubles * 8)), std::max(lp, (int) (SweepLds<4>::doubles * 8))};
 			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<2>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[1]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<4>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[2]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[1]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[2]) == hipSuccess;
 #endif
 			lim.prune = lp;
 		}
 		const int la[3] = {alpha_lds(64, nav->cutcap).bytes, alpha_lds(128, nav->cutcap).bytes, alpha_lds(256, nav->cutcap).bytes};
 		if (la[0] > lim.alpha[0]) {
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<1>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[0], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[0], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll_grad<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
 			lim.alpha[0] = la[0];
 		}
 		if (la[1] > lim.alpha[1]) {
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<2>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[1], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[1], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll_grad<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
 			lim.alpha[1] = la[1];
 		}
 		if (la[2] > lim.alpha[2]) {
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<4>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[2], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
+			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[2], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
 			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll_grad<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
 			lim.alpha[2] = la[2];
@@ -931,11 +960,14 @@ phd_navigator* phd_create(const phd_params* params, int device)
 		// the one-launch chain: its bodies share one pool, the largest of their layouts, which must fit a workgroup (160 KB)
 		// with the kernel's few static words; where it does not (a large MaxQuantity) the separate kernels run
 		const int lc[3] = {chain_lds_bytes<1>(nav->cutcap), chain_lds_bytes<2>(nav->cutcap), chain_lds_bytes<4>(nav->cutcap)};
-		const void* chainfn[4] = {(const void*) k_particle_chain<1>, (const void*) k_particle_chain<2>, (const void*) k_particle_chain<4>,
-		                          (const void*) k_particle_chain<1, true>};
-		bool fits[4] = {false, false, false, false};
-		for (int z = 0; z < 4 && ok; z++) {
-			const int zl = z == 3 ? 0 : z;   // (the HALF build of the one-block chain shares its layout)
+		// (entries 4..7: the same kernels compiled for a depth map, phd_set_depth_map; the chain runs only where both fit)
+		const void* chainfn[8] = {(const void*) k_particle_chain<1>, (const void*) k_particle_chain<2>, (const void*) k_particle_chain<4>,
+		                          (const void*) k_particle_chain<1, true>,
+		                          (const void*) k_particle_chain<1, false, true>, (const void*) k_particle_chain<2, false, true>,
+		                          (const void*) k_particle_chain<4, false, true>, (const void*) k_particle_chain<1, true, true>};
+		bool fits[8] = {false, false, false, false, false, false, false, false};
+		for (int z = 0; z < 8 && ok; z++) {
+			const int zl = (z & 3) == 3 ? 0 : (z & 3);   // (the HALF build of the one-block chain shares its layout)
 			hipFuncAttributes fc;
 			if (hipFuncGetAttributes(&fc, chainfn[z]) != hipSuccess) { ok = false; break; }
 			if ((size_t) fc.sharedSizeBytes + (size_t) lc[zl] + 256 > 160 * 1024) continue;
@@ -945,9 +977,9 @@ phd_navigator* phd_create(const phd_params* params, int device)
 			}
 			fits[z] = true;
 		}
-		nav->chain_ok[0] = fits[0] && fits[3];
-		nav->chain_ok[1] = fits[1];
-		nav->chain_ok[2] = fits[2];
+		nav->chain_ok[0] = fits[0] && fits[3] && fits[4] && fits[7];
+		nav->chain_ok[1] = fits[1] && fits[5];
+		nav->chain_ok[2] = fits[2] && fits[6];
 		ok = ok && hipFuncSetAttribute((const void*) k_plan_migration, hipFuncAttributeMaxDynamicSharedMemorySize, PLAN_LDS_MAX + 1024) == hipSuccess;
 		hipFuncAttributes fa;
 		if (ok && hipFuncGetAttributes(&fa, (const void*) k_normalise_resample) == hipSuccess) {
@@ -1001,6 +1033,11 @@ void phd_destroy(phd_navigator* nav)
 		if (nav->ev_stage[i]) hipEventDestroy(nav->ev_stage[i]);
 	}
 	hipFree(nav->d_stage);
+	for (int i = 0; i < 2; i++) {
+		if (nav->h_depth[i]) hipHostFree(nav->h_depth[i]);
+		if (nav->ev_depth[i]) hipEventDestroy(nav->ev_depth[i]);
+	}
+	hipFree(nav->d_depth);
 	if (nav->own_stream) hipStreamDestroy(nav->own_stream);
 	for (int i = 0; i < phd_navigator::MAXSPLIT - 1; i++) {
 		if (nav->aux[i]) hipStreamDestroy(nav->aux[i]);
@@ -1363,6 +1400,78 @@ int phd_set_measurements(phd_navigator* nav, const double* z3, int nmeasurements
 		stage_release(nav);
 	}
 	nav->M = nmeasurements;
+	return PHD_OK;
+}
+
+// The depth map of the Kinect model. Validated in full before anything changes; a (re)allocation waits for the handle's
+// streams (the kernels of posted steps may still read the old buffer) and the new buffers exist before the old ones go, so that a
+// failed allocation leaves the previous map in place. Otherwise asynchronous: the frame goes through a pinned slot (whose previous copy
+// has finished: its event) into the device buffer on the handle's stream, behind every kernel of the steps posted before (the
+// stream the next step forks from is ordered behind all of them, phd_step_async) and before those of the next.
+int phd_set_depth_map(phd_navigator* nav, const float* depth, int width, int height)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->prm.model != PHD_MODEL_PRM3D) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_depth_map: the depth map belongs to the PRM3D model (KinectMeasurer)");
+	const bool off = !depth && width == 0 && height == 0;
+	if (!off && (!depth || width < 1 || width > PHD_DEPTH_MAX || height < 1 || height > PHD_DEPTH_MAX)) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_depth_map: width and height in 1..4096 with a buffer, or NULL with 0 x 0 (no map)");
+	}
+	if (nav->multi) return multi_set_depth_map(nav, depth, width, height);
+	enter(nav);
+	if (off) {
+		nav->dp.depth = nullptr; nav->dp.depth_w = 0; nav->dp.depth_h = 0; nav->dp.depth_hx = 0; nav->dp.depth_hy = 0;
+		return PHD_OK;
+	}
+	const size_t n = (size_t) width * height;
+	if (n > nav->depthcap || n > nav->hdepthcap) {
+		HC(hipStreamSynchronize(nav->stream));
+		for (int s = 0; s < phd_navigator::MAXSPLIT - 1; s++) if (nav->aux[s]) HC(hipStreamSynchronize(nav->aux[s]));
+		float* nd = nullptr; float* nh[2] = {nullptr, nullptr};
+		hipError_t e = hipMalloc((void**) &nd, n * 4);
+		for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**) &nh[i], n * 4, hipHostMallocDefault);
+		for (int i = 0; i < 2 && e == hipSuccess; i++) if (!nav->ev_depth[i]) e = hipEventCreateWithFlags(&nav->ev_depth[i], hipEventDisableTiming);
+		if (e != hipSuccess) {
+			hipFree(nd);
+			for (int i = 0; i < 2; i++) if (nh[i]) hipHostFree(nh[i]);
+			return nav->fail(PHD_ERR_DEVICE, std::string("phd_set_depth_map: allocation: ") + hipGetErrorString(e));
+		}
+		hipFree(nav->d_depth);
+		for (int i = 0; i < 2; i++) if (nav->h_depth[i]) hipHostFree(nav->h_depth[i]);
+		nav->d_depth = nd; nav->depthcap = n;
+		nav->h_depth[0] = nh[0]; nav->h_depth[1] = nh[1]; nav->hdepthcap = n;
+		nav->depth_used[0] = nav->depth_used[1] = false;
+	}
+	nav->depth_i ^= 1;
+	const int i = nav->depth_i;
+	if (nav->depth_used[i]) HC(hipEventSynchronize(nav->ev_depth[i]));
+	std::memcpy(nav->h_depth[i], depth, n * 4);
+	HC(hipMemcpyAsync(nav->d_depth, nav->h_depth[i], n * 4, hipMemcpyHostToDevice, nav->stream));
+	HC(hipEventRecord(nav->ev_depth[i], nav->stream));
+	nav->depth_used[i] = true;
+	nav->dp.depth = nav->d_depth; nav->dp.depth_w = width; nav->dp.depth_h = height;
+	nav->dp.depth_hx = (double) ((float) width / 2.0f); nav->dp.depth_hy = (double) ((float) height / 2.0f);   // ResX / 2 (KinectMeasurer.cs:153)
+	return PHD_OK;
+}
+
+int phd_test_detection_probability(phd_navigator* nav, const double* z3, int n, double* out)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);
+	if (n < 0 || (n > 0 && (!z3 || !out))) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_test_detection_probability: n >= 0 points and both buffers");
+	if (n == 0) return PHD_OK;
+	enter(nav);
+	double* dz = nullptr; double* dout = nullptr;
+	HC(hipMalloc((void**) &dz, (size_t) n * 3 * 8));
+	hipError_t e = hipMalloc((void**) &dout, (size_t) n * 8);
+	if (e == hipSuccess) e = hipMemcpyAsync(dz, z3, (size_t) n * 3 * 8, hipMemcpyHostToDevice, nav->stream);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(k_test_detection_probability, dim3((n + 255) / 256), dim3(256), 0, nav->stream, nav->dp, (const double*) dz, n, dout);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t) n * 8, hipMemcpyDeviceToHost, nav->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(nav->stream);
+	hipFree(dz); hipFree(dout);
+	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_detection_probability: ") + hipGetErrorString(e));
 	return PHD_OK;
 }
 

@@ -106,6 +106,13 @@ public:
 		return out;
 	}
 
+	// KinectMeasurer's current depth frame (phd_set_depth_map): `depth` row-major [height][width] (the reference's
+	// float[ResX][ResY] frame transposed), used by every step until the next call; an empty vector switches it off
+	void setDepthMap(const std::vector<float>& depth, int width, int height)
+	{
+		check(depth.empty() ? phd_set_depth_map(nav_, nullptr, 0, 0) : phd_set_depth_map(nav_, depth.data(), width, height));
+	}
+
 	// ≙ SlamUpdate (:323-362); `uniform` replaces (double) Util.Uniform.Next() of ResampleParticles (:727)
 	void SlamUpdate(const std::vector<PixelRangeMeasurement>& measurements, double uniform)
 	{

@@ -213,6 +213,27 @@ class PHDNavigator:
         g = (ll[:, :, 0] - ll[:, :, 1]) / (2 * eps)
         return g[0] if len(g) == 1 else g
 
+    def set_depth_map(self, depth):
+        """The current Kinect depth frame (phd_set_depth_map): a (height, width) array, row-major depth[y][x] — the reference's
+        float[ResX][ResY] frame transposed —, taken as float32; NaN means no reading. Every step after this call uses it until
+        the next; None switches it off (the PRM3D detection probability again)."""
+        if depth is None:
+            self._check(self._lib.phd_set_depth_map(self._h, None, 0, 0))
+            return
+        d = np.ascontiguousarray(depth, np.float32)
+        if d.ndim != 2:
+            raise ValueError("the depth map is a (height, width) array")
+        self._check(self._lib.phd_set_depth_map(self._h, d.ctypes.data_as(C.POINTER(C.c_float)), int(d.shape[1]), int(d.shape[0])))
+
+    def DetectionProbabilityM(self, z):
+        """≙ SimulatedVehicle.DetectionProbabilityM (SimulatedVehicle.cs:336) at pixel-range points z[n][3], evaluated by the
+        device function the step uses, with the handle's parameters and current depth map (phd_test_detection_probability)."""
+        z = np.ascontiguousarray(z, np.float64).reshape(-1, 3)
+        out = np.zeros(len(z))
+        if len(z):
+            self._check(self._lib.phd_test_detection_probability(self._h, _ptr(z), len(z), _ptr(out)))
+        return out
+
     def SlamUpdate(self, time, measurements, u_resample=0.5):
         """≙ PHDNavigator.SlamUpdate (:323-362)."""
         z = np.ascontiguousarray(measurements, np.float64).reshape(-1, 3)
