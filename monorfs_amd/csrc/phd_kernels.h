@@ -381,7 +381,11 @@ __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, 
 		alpha_assoc_body<ZB, false, false, 1, 0, DEPTH>(prm, a, cutcap, smem, nullptr, -1, a.dsplit ? &s_hgo : nullptr);
 		__syncthreads();
 		PHD_STAMP(4);
-		if (!s_hgo) alpha_density_body(prm, a, smem);
+		// (every wave takes the flag into a register before thread 0 may reuse the word for alpha_meet's answer: without the
+		// barrier a late wave could read that answer instead and take the other branch alone)
+		const int hgo = s_hgo;
+		__syncthreads();
+		if (!hgo) alpha_density_body(prm, a, smem);
 		else {
 			// (the helper has the sums: this workgroup's number is the set log-likelihood it has just written)
 			if (threadIdx.x == 0) {

@@ -16,7 +16,8 @@
  *              order, MurtyNode children, connected components, AssignmentValue
  *              (GraphCombinatoricsTest.cs:66-404); systematic resampling (SimulationTest.cs:225-270).
  *   UNPINNED : WeightAlpha, BestMapEstimate, SetLogLikelihood values, the PRM3D measurement model
- *              inside CorrectConditional and FuzzyVisibleM have no numeric test in the reference;
+ *              inside CorrectConditional, FuzzyVisibleM and KinectMeasurer's depth-map rule (orc_set_depth_map)
+ *              have no numeric test in the reference;
  *              for those this file's reading of the source is the definition ("parity unpinned").
  *
  * Third-party arithmetic that is not under /root/reference and is replaced by a stated
@@ -347,8 +348,46 @@ double fuzzy_visible(const Model& md, const double* z)
 	return std::max(0.0, std::min(1.0, mind));
 }
 
-// SimulatedVehicle.DetectionProbabilityM / DetectionProbability (SimulatedVehicle.cs:324-339)
-double pd_m(const Model& md, const double* z) { return fuzzy_visible(md, z) * md.p->pd; }
+// KinectMeasurer's depth frame (orc_set_depth_map): row-major depth[y][x] float32, the layout phd_set_depth_map takes
+// (include/phdhip.h); empty = no map. Written only by orc_set_depth_map, between calls: every parallel region reads it.
+std::vector<float> g_depth;
+int g_depth_w = 0, g_depth_h = 0;
+
+// System.Math.Min / Max on doubles: NaN if either argument is NaN (std::min / max would return one of the two)
+double net_min(double a, double b) { return (std::isnan(a) || std::isnan(b)) ? std::numeric_limits<double>::quiet_NaN() : std::min(a, b); }
+double net_max(double a, double b) { return (std::isnan(a) || std::isnan(b)) ? std::numeric_limits<double>::quiet_NaN() : std::max(a, b); }
+
+// KinectMeasurer.FuzzyVisibleM (KinectMeasurer.cs:151-173) on top of the PRM3D value `base` (base.FuzzyVisibleM, :157).
+// ResX / ResY are floats (:48-53), so ResX / 2 is a float32 division; the range is cast to float (:155) and the two
+// subtractions are float32, each divided by the double VisibilityRamp[2]. The reference indexes a jagged depth[x][y]; the
+// library's frame is row-major depth[y][x]. Where the reference would throw (a pixel outside the frame) the library gives 0.
+double kinect_visible(const Model& md, const double* z, double base)
+{
+	const int   w = g_depth_w, h = g_depth_h;
+	const double xd = z[0] + (double) ((float) w / 2.0f);
+	const double yd = z[1] + (double) ((float) h / 2.0f);
+	const float range = (float) z[2];
+	if (base == 0) return 0;   // outside of the image region (:159-161)
+	if (!(xd > -1.0 && xd < w && yd > -1.0 && yd < h)) return 0;   // (int) truncates toward zero: (-1, 0) is pixel 0
+	const int x = (int) xd, y = (int) yd;
+	const float d = g_depth[(size_t) y * w + x];
+	if (std::isnan(d)) return 0;   // :165-167
+	const float  rmin = (float) md.p->measurer[1];   // RangeClip.Min, an AForge.Range of float32
+	const double ramp = md.p->visibility_ramp[2];
+	double mind = base;
+	mind = net_min(mind, (range - rmin) / ramp);   // :169
+	mind = net_min(mind, (d - range) / ramp);      // :170
+	return net_max(0, net_min(1, mind));
+}
+
+// SimulatedVehicle.DetectionProbabilityM / DetectionProbability (SimulatedVehicle.cs:324-339): FuzzyVisibleM * PD, with
+// KinectMeasurer's FuzzyVisibleM while a depth map is set (PRM3D only: the Kinect measurer is a PRM3D one)
+double pd_m(const Model& md, const double* z)
+{
+	double v = fuzzy_visible(md, z);
+	if (!g_depth.empty() && md.p->model == PHD_MODEL_PRM3D) v = kinect_visible(md, z, v);
+	return v * md.p->pd;
+}
 
 double pd_landmark(const Model& md, const Pose& pose, const double* lm)
 {
@@ -1359,6 +1398,27 @@ double orc_detection_probability(const phd_params* p, const double* pose7, const
 {
 	Model md = make_model(p);
 	return pd_landmark(md, make_pose(pose7), lm);
+}
+// DetectionProbabilityM at n pixel-range points z3[n][3] -> out[n]
+void orc_detection_probability_m(const phd_params* p, const double* z3, int n, double* out)
+{
+	Model md = make_model(p);
+	for (int i = 0; i < n; i++) out[i] = pd_m(md, z3 + (size_t) i * 3);
+}
+// The Kinect depth frame every later call uses (row-major depth[height][width], copied); depth == nullptr clears it.
+// Returns 0, or 1 for a bad size (the map is then left as it was). Not to be called while another call runs.
+int orc_set_depth_map(const float* depth, int width, int height)
+{
+	if (!depth) {
+		g_depth.clear();
+		g_depth_w = g_depth_h = 0;
+		return 0;
+	}
+	if (width <= 0 || height <= 0) return 1;
+	g_depth.assign(depth, depth + (size_t) width * height);
+	g_depth_w = width;
+	g_depth_h = height;
+	return 0;
 }
 void orc_quat_matrix(const double* q4, double* r9) { qmatrix(Quat{q4[0], q4[1], q4[2], q4[3]}, r9); }
 void orc_quat_rotate(const double* q4, const double* v3, double* o3)

@@ -64,3 +64,30 @@ def occluding_map(rng, width, height, near=0.5, far=1.5, blocks=(8, 6), holes=0.
     d = cell[ys[:, None], xs[None, :]].copy()
     d[rng.uniform(size=d.shape) < holes] = np.nan
     return d
+
+
+def probe_points(rng, w, h, n):
+    """n pixel-range points over a w x h image and 12 pixels beyond each side, ranges in [0, 4.2]; a quarter of them on a
+    pixel edge exactly or one ulp either side of it"""
+    hx, hy = w / 2, h / 2
+    z = np.column_stack([rng.uniform(-hx - 12, hx + 12, n), rng.uniform(-hy - 12, hy + 12, n), rng.uniform(0.0, 4.2, n)])
+    k = n // 4   # pixel edges: exactly on a cell boundary and one ulp either side
+    ex = rng.integers(-int(hx) - 2, int(hx) + 2, k).astype(float)
+    ey = rng.integers(-int(hy) - 2, int(hy) + 2, k).astype(float)
+    side = rng.integers(0, 3, (k, 2))
+    ex = np.where(side[:, 0] == 0, np.nextafter(ex, -np.inf), np.where(side[:, 0] == 1, ex, np.nextafter(ex, np.inf)))
+    ey = np.where(side[:, 1] == 0, np.nextafter(ey, -np.inf), np.where(side[:, 1] == 1, ey, np.nextafter(ey, np.inf)))
+    z[:k, 0], z[:k, 1] = ex, ey
+    return z
+
+
+def probe_map(rng, w, h):
+    """a w x h map of depths in [0, 4.5] with NaN, +inf, -inf, 0 and below-RangeClip.Min pixels among them"""
+    d = rng.uniform(0.0, 4.5, (h, w)).astype(np.float32)
+    kind = rng.integers(0, 8, (h, w))
+    d[kind == 0] = np.nan
+    d[kind == 1] = np.inf
+    d[kind == 2] = -np.inf
+    d[kind == 3] = 0.0
+    d[kind == 4] = np.float32(0.05)   # below RangeClip.Min
+    return d

@@ -1,4 +1,5 @@
 """ctypes access to the CPU oracle (oracle/libphd_oracle.so). Test infrastructure only."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -291,6 +292,36 @@ def detection_probability(p, pose7, lm):
     pose7 = np.ascontiguousarray(pose7, np.float64)
     lm = np.ascontiguousarray(lm, np.float64)
     return lib.orc_detection_probability(C.byref(p), pose7.ctypes.data_as(dp), lm.ctypes.data_as(dp))
+
+
+def detection_probability_m(p, z):
+    """DetectionProbabilityM at pixel-range points z[n][3] (with the depth map of set_depth_map, if any)"""
+    z = np.ascontiguousarray(z, np.float64).reshape(-1, 3)
+    out = np.zeros(len(z))
+    lib.orc_detection_probability_m(C.byref(p), z.ctypes.data_as(dp), len(z), out.ctypes.data_as(dp))
+    return out
+
+
+def set_depth_map(depth):
+    """KinectMeasurer's depth frame for every later oracle call: a row-major float32 depth[y][x] (include/phdhip.h,
+    phd_set_depth_map), copied; None clears it. Prefer `depth_map`, which clears it again."""
+    if depth is None:
+        lib.orc_set_depth_map(None, 0, 0)
+        return
+    d = np.ascontiguousarray(depth, np.float32)
+    assert d.ndim == 2
+    if lib.orc_set_depth_map(d.ctypes.data_as(C.POINTER(C.c_float)), d.shape[1], d.shape[0]) != 0:
+        raise ValueError("bad depth map shape %r" % (d.shape,))
+
+
+@contextlib.contextmanager
+def depth_map(depth):
+    """with orc.depth_map(d): ... — the oracle sees `d` inside the block and no map after it, whatever happens"""
+    set_depth_map(depth)
+    try:
+        yield
+    finally:
+        set_depth_map(None)
 
 
 class State:

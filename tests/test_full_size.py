@@ -1,6 +1,9 @@
-"""BASELINE.json's full sizes on the GPU, through the C-ABI: size-independent properties of the step plus an
-oracle check on a sample of particles (the whole oracle step at these sizes takes minutes on the host).
+"""BASELINE.json's full sizes on the GPU, through the C-ABI: size-independent properties of the step, an oracle check
+on a sample of particles stage by stage, and whole steps with every particle against the oracle (one oracle step takes
+0.7 s at B and 5.7 s at S on 16 host threads).
   B: 2048 particles x 512 components x 64 measurements      S: 4096 x 1024 x 128, MaxQuantity 1024"""
+import os
+
 import numpy as np
 import pytest
 
@@ -9,6 +12,9 @@ pytestmark = pytest.mark.gpu
 import orc
 from monorfs_amd.abi import prm3d_defaults
 from monorfs_amd.synth import CONFIGS, Frame
+from oracle_parity import assert_step_matches, oracle_state
+
+THREADS = min(16, os.cpu_count() or 1)   # (the oracle's threads: a command on the GPU machines gets 16 CPUs)
 
 
 def setup(cfg, profile):
@@ -77,6 +83,62 @@ def test_full_size_step_resamples_consistently():
     assert all(np.array_equal(x, y) for x, y in zip(m1, m2))
     nav.close()
     nav2.close()
+
+
+def test_B_steady_three_steps_every_particle_against_the_oracle():
+    """Config B (the frame of bench.py, with the steady weights): three steps with perturbed measurements and varying u, at
+    least one of which resamples (particles and their maps are copied), every particle against the oracle after every step
+    (tests/oracle_parity.py). The separate-kernel path (2048 particles: above chain_max), the fused emit + prune (64
+    measurements) and the grid resampling kernels. Cost on one MI355X box: 2.1 s, nearly all of it the oracle's three
+    steps (0.7 s each on 16 threads); the device's steps and the bulk reads are a small part."""
+    nav, p, f = setup("B", "steady")
+    st = oracle_state(f, p.max_quantity)
+    rng = np.random.default_rng(1002)
+    nres = 0
+    for step in range(3):
+        z = f.z + rng.normal(size=f.z.shape) * np.sqrt([2.0, 2.0, 1e-3]) * 0.2 * step
+        u = float(rng.uniform(0.05, 0.95))
+        best, src, res, _ = orc.slam_update(p, st, z, u=u, threads=THREADS)
+        nav.SlamUpdate(None, z, u_resample=u)
+        assert_step_matches(nav, st, best, src, res, p.max_quantity, "B steady step %d" % step)
+        nres += int(res)
+    assert nres >= 1, "no step resampled"
+    nav.close()
+
+
+@pytest.mark.parametrize("cfg,profile,timed", [("B", "survey", True), ("S", "steady", False), ("S", "survey", True)])
+def test_full_size_step_every_particle_against_the_oracle(cfg, profile, timed):
+    """One step of the full-size frame, every particle against the oracle (tests/oracle_parity.py); with `timed`, the mode
+    bench.py times (phd_set_all_pairs + phd_set_frozen, steps posted back to back) against the same oracle step.
+    On these frames every WeightAlpha underflows to 0 (the expected map size exceeds what the frame explains by far; the
+    reference's double arithmetic does the same), and both sides must then agree on what follows: the weights are all
+    exactly 0 (the reference divides by the sum only when it is not 0: 0 / 1), nothing is depleted, no resampling, the
+    sources are the identity and BestParticle is particle 0 (no weight above 0). S is the other BASELINE size: 4096 x
+    1024 x 128, the unfused emit and prune at 128 measurements. Cost on one MI355X box, the oracle on 16 threads: B survey
+    (with the timed handle) 1.3 s, of which the oracle's step is 0.7 s; S steady 6.0 s and S survey (with the timed handle)
+    7.1 s, of which the oracle's step is 5.7 s; the rest is the device's steps and reading 4096 maps back."""
+    nav, p, f = setup(cfg, profile)
+    st = oracle_state(f, p.max_quantity)
+    best, src, res, alpha = orc.slam_update(p, st, f.z, u=0.41, threads=THREADS)
+    nav.SlamUpdate(None, f.z, u_resample=0.41)
+    what = "%s %s" % (cfg, profile)
+    assert_step_matches(nav, st, best, src, res, p.max_quantity, what)
+    if profile == "survey":
+        assert np.all(alpha == 0), "survey frame: a WeightAlpha did not underflow"
+    if np.all(alpha == 0):
+        assert np.all(nav.VehicleWeights == 0) and not res and best == 0
+        assert np.array_equal(nav.resample_sources()[0], np.arange(f.P))
+    nav.close()
+    if timed:
+        timed_nav, _, _ = setup(cfg, profile)
+        timed_nav.set_measurements(f.z)
+        timed_nav.set_frozen(True)
+        timed_nav.set_all_pairs(True)
+        for _ in range(2):   # (frozen: the second step reads the same input as the first)
+            timed_nav.step_async(0.41)
+        timed_nav.sync()
+        assert_step_matches(timed_nav, st, best, src, res, p.max_quantity, what + " timed", bulk=False)
+        timed_nav.close()
 
 
 class _Dev:

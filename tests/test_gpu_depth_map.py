@@ -77,30 +77,6 @@ def occluder(seed, w=W, h=H):
 
 
 # ---- 1. the probe -----------------------------------------------------------------------------------------------
-def probe_points(rng, w, h, n):
-    hx, hy = w / 2, h / 2
-    z = np.column_stack([rng.uniform(-hx - 12, hx + 12, n), rng.uniform(-hy - 12, hy + 12, n), rng.uniform(0.0, 4.2, n)])
-    k = n // 4   # pixel edges: exactly on a cell boundary and one ulp either side
-    ex = rng.integers(-int(hx) - 2, int(hx) + 2, k).astype(float)
-    ey = rng.integers(-int(hy) - 2, int(hy) + 2, k).astype(float)
-    side = rng.integers(0, 3, (k, 2))
-    ex = np.where(side[:, 0] == 0, np.nextafter(ex, -np.inf), np.where(side[:, 0] == 1, ex, np.nextafter(ex, np.inf)))
-    ey = np.where(side[:, 1] == 0, np.nextafter(ey, -np.inf), np.where(side[:, 1] == 1, ey, np.nextafter(ey, np.inf)))
-    z[:k, 0], z[:k, 1] = ex, ey
-    return z
-
-
-def probe_map(rng, w, h):
-    d = rng.uniform(0.0, 4.5, (h, w)).astype(np.float32)
-    kind = rng.integers(0, 8, (h, w))
-    d[kind == 0] = np.nan
-    d[kind == 1] = np.inf
-    d[kind == 2] = -np.inf
-    d[kind == 3] = 0.0
-    d[kind == 4] = np.float32(0.05)   # below RangeClip.Min
-    return d
-
-
 @pytest.mark.parametrize("which", ["prm3d_640x480", "kinect_160x120"])
 def test_probe_is_the_numpy_reading_bit_for_bit(nav_mod, which):
     rng = np.random.default_rng(11 if which.startswith("prm3d") else 12)
@@ -110,9 +86,9 @@ def test_probe_is_the_numpy_reading_bit_for_bit(nav_mod, which):
     else:
         p, (w, h) = kinect_defaults(1, 600, 8, delta=4)
     nav = nav_mod.PHDNavigator(p, particlecount=1)
-    z = probe_points(rng, w, h, 500000)
+    z = kinect_ref.probe_points(rng, w, h, 500000)
     assert np.array_equal(nav.DetectionProbabilityM(z), kinect_ref.detection_probability(p, z, None))   # no map: PRM3D
-    depth = probe_map(rng, w, h)
+    depth = kinect_ref.probe_map(rng, w, h)
     nav.set_depth_map(depth)
     got = nav.DetectionProbabilityM(z)
     want = kinect_ref.detection_probability(p, z, depth)
