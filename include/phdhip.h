@@ -347,7 +347,9 @@ int   phd_set_stream(phd_navigator* nav, void* stream, uint8_t lend);
  * log-likelihood with everything fully visible (constant PD, gate 12) — for a BATCH of candidate poses against one
  * landmark set and one measurement set: the shape of the smoother's pose searches (LoopyPHDNavigator.cs:777-909).
  * poses7[nposes][7], landmarks3[nlandmarks][3], z3[nmeasurements][3]; out[nposes]. nposes <= max_particles,
- * nlandmarks <= min(1024, max_quantity). Synchronous; does not touch the particle state.                         */
+ * nlandmarks <= min(1024, max_quantity rounded up to a multiple of 64): the landmark scratch of a step's map estimate
+ * (an estimate beyond it is PHD_ERR_CAPACITY there); more landmarks are PHD_ERR_BAD_ARGUMENT. Synchronous; does not
+ * touch the particle state.                                                                                       */
 int phd_quasi_set_loglik(phd_navigator* nav, const double* poses7, int nposes, const double* landmarks3, int nlandmarks,
                          const double* z3, int nmeasurements, double* out);
 

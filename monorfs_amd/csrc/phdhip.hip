@@ -1152,7 +1152,7 @@ static int quasi_batch(phd_navigator* nav, const double* poses7, int nposes, con
 	if (nav->multi) nav = multi_shard0(nav);   // a batch of candidate poses against one landmark set does not touch the particle state
 	if (nposes < 1 || nposes > nav->Pcap || nlandmarks < 0 || nlandmarks > nav->Jcap || nmeasurements < 0 ||
 	    nmeasurements > nav->prm.max_measurements || !poses7 || !out || (nlandmarks && !landmarks3) || (nmeasurements && !z3)) {
-		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_set_loglik: sizes out of range (poses <= max_particles, landmarks <= min(1024, max_quantity), measurements <= max_measurements)");
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_set_loglik: sizes out of range (poses <= max_particles, landmarks <= min(1024, max_quantity rounded up to 64), measurements <= max_measurements)");
 	}
 	FINITE_OR_FAIL(nav, poses7, (size_t) nposes * 7, "phd_quasi_set_loglik");
 	FINITE_OR_FAIL(nav, landmarks3, (size_t) nlandmarks * 3, "phd_quasi_set_loglik");

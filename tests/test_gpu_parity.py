@@ -320,14 +320,23 @@ def test_motion_update_matches_oracle(nav_mod):
     nav.close()
 
 
-@pytest.mark.parametrize("J,M,seed", [(3, 4, 81), (40, 30, 82), (12, 70, 83), (300, 64, 84), (0, 5, 85), (6, 0, 86)])
+# the edges of the quasi kernels' launch shapes: four measurement blocks (129, 256), the landmark arrays in LDS up to 256
+# and in the HBM slab beyond (255 / 256 / 257), the slab at its bound Jcap (640 at max_quantity 600, 1024 at 1100)
+QUASI_EDGES = [(40, 129, 87), (64, 256, 88), (255, 30, 89), (256, 30, 90), (257, 30, 91), (640, 30, 92), (1024, 30, 93)]
+
+
+def quasi_maxq(J):
+    return 1100 if J > 640 else 600
+
+
+@pytest.mark.parametrize("J,M,seed", [(3, 4, 81), (40, 30, 82), (12, 70, 83), (300, 64, 84), (0, 5, 85), (6, 0, 86)] + QUASI_EDGES)
 def test_quasi_set_log_likelihood_batch(nav_mod, J, M, seed):
     """QuasiSetLogLikelihood for a batch of candidate poses (phd_quasi_set_loglik) against the oracle:
     small and large clusters (the gate of 12 joins more measurements than the gate of 5), a landmark set larger than
     the LDS-resident limit, empty sets."""
     rng = np.random.default_rng(seed)
     f = Frame(48, max(J, 1), max(M, 1), seed, weight_profile="steady")
-    nav, p = make_nav(nav_mod, f)
+    nav, p = make_nav(nav_mod, f, maxq=quasi_maxq(J))
     lm = f.mean[0, :J].copy()
     z = f.z[:M].copy()
     if M > 3 and J > 3:
@@ -343,7 +352,8 @@ def test_quasi_set_log_likelihood_batch(nav_mod, J, M, seed):
 
 
 @pytest.mark.parametrize("J,M,seed", [(3, 4, 181), (40, 30, 182), (12, 70, 183), (300, 64, 184), (0, 5, 185), (6, 0, 186), (2, 3, 187),
-                                      (64, 60, 188), (110, 100, 189)])   # ... more clusters than one run of the ordered pass takes (32), than its LDS copy holds (64)
+                                      (64, 60, 188), (110, 100, 189)]   # ... more clusters than one run of the ordered pass takes (32), than its LDS copy holds (64)
+                         + [(J, M, seed + 103) for J, M, seed in QUASI_EDGES])
 @pytest.mark.parametrize("mode", [0, 1])
 def test_quasi_set_log_likelihood_gradient_batch(nav_mod, J, M, seed, mode):
     """Row f4, gradient part: QuasiSetLogLikelihood(..., out gradient) (PHDNavigator.cs:543-713) for a batch of poses
@@ -352,7 +362,7 @@ def test_quasi_set_log_likelihood_gradient_batch(nav_mod, J, M, seed, mode):
     landmarks (`modelsize` cuts the enumeration), a landmark set beyond the LDS-resident limit, empty sets."""
     rng = np.random.default_rng(seed)
     f = Frame(48, max(J, 1), max(M, 1), seed, weight_profile="steady")
-    nav, p = make_nav(nav_mod, f)
+    nav, p = make_nav(nav_mod, f, maxq=quasi_maxq(J))
     lm = f.mean[0, :J].copy()
     z = f.z[:M].copy()
     if M > 3 and J > 3:
