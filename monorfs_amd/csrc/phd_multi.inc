@@ -186,9 +186,7 @@ static void multi_issue_step(MultiState* m, int s, long long k, const MultiCmd& 
 		if (!rc) {
 			// every record straight into its place in the receiver's buffer (how many there are is known on the device)
 			StepBufs b = make_bufs(a);
-			timer_begin(a, T_PK);
-			hipLaunchKernelGGL(k_pack_particles, dim3(pack_grid(a)), dim3(256), 0, a->stream, b, a->plan, n, (double*) nullptr, (double* const*) a->d_recv_tab);
-			timer_end(a, T_PK);
+			launch_timed(a, T_PK, a->stream, false, k_pack_particles, dim3(pack_grid(a)), dim3(256), 0, b, a->plan, n, (double*) nullptr, (double* const*) a->d_recv_tab);
 			if (hipGetLastError() != hipSuccess) rc = a->fail(PHD_ERR_DEVICE, "k_pack_particles");
 		}
 		if (!rc && hipEventRecord(m->ev_pack[par][s], a->stream) != hipSuccess) rc = a->fail(PHD_ERR_DEVICE, "hipEventRecord (pack)");

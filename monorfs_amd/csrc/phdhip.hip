@@ -13,6 +13,8 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -32,6 +34,35 @@ struct Timer {          // one record per kernel launch since the last phd_timin
 	int         t0_from;   // >= 0: the launch starts where record t0_from ended (back-to-back on one stream: one event, not two)
 };
 
+// What a handle allocates, released when its owner goes (move-only); the owner converts to the raw pointer wherever one is
+// read. K says how one kind of resource is made and released. The device of the handle must be current when an owner goes.
+struct DevMem  { static hipError_t make(void** p, size_t bytes, unsigned) { return hipMalloc(p, bytes); } static void drop(void* p) { hipFree(p); } };
+struct PinMem  { static hipError_t make(void** p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); } static void drop(void* p) { hipHostFree(p); } };
+struct EventK  { static void drop(hipEvent_t e) { hipEventDestroy(e); } };
+struct StreamK { static void drop(hipStream_t s) { hipStreamDestroy(s); } };
+
+template <class T, class K>
+class Owned {
+	T* p_ = nullptr;
+public:
+	using element = T;
+	Owned() = default;
+	Owned(const Owned&) = delete;
+	Owned& operator=(const Owned&) = delete;
+	Owned(Owned&& o) noexcept : p_(o.release()) {}
+	Owned& operator=(Owned&& o) noexcept { if (this != &o) reset(o.release()); return *this; }
+	~Owned() { reset(); }
+	operator T*() const { return p_; }
+	void reset(T* p = nullptr) { if (p_) K::drop(p_); p_ = p; }
+	T* release() { T* p = p_; p_ = nullptr; return p; }   // (gives the resource up without releasing it)
+	T** put() { reset(); return &p_; }                   // for the runtime's creating calls with an out-parameter
+	hipError_t alloc(size_t count, unsigned flags = 0) { return K::make((void**) put(), count * sizeof(T), flags); }   // `count` elements; what it held goes first
+};
+template <class T> using DevBuf = Owned<T, DevMem>;
+template <class T> using PinBuf = Owned<T, PinMem>;
+using Event  = Owned<ihipEvent_t, EventK>;
+using Stream = Owned<ihipStream_t, StreamK>;
+
 }  // namespace
 
 struct MultiState;   // phd_create_multi: the shards of a multi-device handle (phd_multi.inc)
@@ -42,7 +73,7 @@ struct phd_navigator {
 	DevParams   dp;
 	int         device = 0;
 	hipStream_t stream = nullptr;      // the stream every kernel of this handle is launched on
-	hipStream_t own_stream = nullptr;  // created by phd_create; `stream` unless the host lent its own
+	Stream      own_stream;            // created by phd_create; `stream` unless the host lent its own (a lent stream is not the handle's to destroy)
 	static const int MAXSPLIT = 4;
 	int         nsplit = 0;            // sub-ranges a step's per-particle kernels are split into (0: chosen from the particle count)
 	int         dsplit_max = 256;      // ... and up to this many, with a helper workgroup per particle for the densities of WeightAlpha (two workgroups per
@@ -50,11 +81,11 @@ struct phd_navigator {
 	int         dsplit_late = 0;       // env PHD_DSPLIT_LATE (tests and measurements; StepBufs::dsplit = 1 + this): 1 the helpers report 0.5 ms late, 2 they leave at once,
 	                                   // 3 they report and wait but are never picked — in all three every main workgroup keeps its density sums
 	unsigned int dseq = 0;             // launches of the chain with helpers so far (StepBufs::dstamp)
-	unsigned int* d_dsync = nullptr;   // the helpers' words (StepBufs); DSPLIT_ROWS particles
+	DevBuf<unsigned int> d_dsync;      // the helpers' words (StepBufs); DSPLIT_ROWS particles
 	int         chain_max = 512;       // up to this many particles a step's per-particle kernels run as one launch (k_particle_chain; env PHD_CHAIN_MAX)
 	int         fold_nr = 0;           // 1 (env PHD_FOLD_NR): the chain ends the step itself — k_normalise_resample's body in its last workgroup; measured slower than the launch
 	bool        chain_ok[3] = {false, false, false};   // ... where the bodies' LDS arrays fit one workgroup (per measurement-block count 1, 2, 4)
-	hipStream_t aux[MAXSPLIT - 1] = {nullptr, nullptr, nullptr};   // streams of the sub-ranges after the first
+	Stream      aux[MAXSPLIT - 1];     // streams of the sub-ranges after the first
 	// Option (environment PHD_DEFER_BIG=1; off by default): the particles with an association cluster of more than
 	// ALPHA_DEFER_ROWS rows are listed by k_alpha_assoc_main and their ordered replay runs inside the launch of the densities
 	// (the first workgroups of k_alpha_density_big), k_normalise_resample / k_push_weights finish alpha. Built when the replay
@@ -67,18 +98,17 @@ struct phd_navigator {
 	int         fuse_ep = -1;          // k_emit_finish and k_prune_merge as one launch (k_emit_prune): -1 = for frames of up to 64 measurements (measured on
 	                                   // two streams: config B 0.677 -> 0.667 ms survey, 0.634 -> 0.615 steady; config S, 128 measurements, 3.67 -> 3.85:
 	                                   // its Kalman path is long and pays for the 128 registers); environment PHD_FUSE_EP = 0 / 1 forces
-	int         fuse_sep = 0;          // builds with -DPHD_WITH_FUSE_SEP only, environment PHD_FUSE_SEP=1: k_sweep, k_emit_finish and k_prune_merge as one launch
 	int         last_defer = 0;        // the last launch_map left alpha open (k_normalise_resample / k_push_weights / k_alpha_combine finish it)
-	int*        d_biglist = nullptr;   // [MAXSPLIT][Pcap + 2]
-	double*     d_ratio = nullptr;     // [Pcap]
-	hipEvent_t  ev_fork = nullptr, ev_join[MAXSPLIT - 1] = {nullptr, nullptr, nullptr};
+	DevBuf<int>    d_biglist;          // [MAXSPLIT][Pcap + 2]
+	DevBuf<double> d_ratio;            // [Pcap]
+	Event       ev_fork, ev_join[MAXSPLIT - 1];
 	// Two sub-ranges, steps posted back to back (phd_step_async after phd_step_async): the end of the step runs on the stream
 	// whose chain finishes LAST and no fork precedes the next step ("the step boundary"; env PHD_PIPELINE=0: a fork
 	// before and a join behind every step, as for every other caller)
 	int         pipeline = 1;
 	bool        pipe_ok = false;       // nothing was enqueued on `stream` since the last such step: the aux stream is ordered behind all of it
 	int         lagger = 1;            // which of the two streams (0 `stream`, 1 aux[0]) finishes the coming step last
-	hipEvent_t  ev_res = nullptr;      // k_normalise_resample is through (recorded on the stream that ran it)
+	Event       ev_res;                // k_normalise_resample is through (recorded on the stream that ran it)
 	int         device_order = 0;      // 1 (env PHD_DEVICE_ORDER): between such steps no event at all — k_normalise_resample counts the tickets of both
 	                                   // streams' k_alpha_density workgroups, the other stream's next k_sweep waits behind k_gate. Measured 0.2 % faster
 	                                   // than the events; two kernels that poll are not worth that by default
@@ -90,64 +120,66 @@ struct phd_navigator {
 	bool frozen = false;
 	bool all_pairs = false;            // phd_set_all_pairs: the benchmark mode of SURVEY §8d
 
-	Bank   bank[3];
-	int*   d_sel = nullptr;      // [2][SEL_STRIDE]: roles for the current / next step (+ where the last result is)
-	int*   d_mslot = nullptr;    // [Pcap] sharded step: slot of every particle's mixture in the OUT bank
+	Bank   bank[3];              // (plain pointers: kernels take it by value; its arrays are owned beside it)
+	DevBuf<double> bank_mix[3], bank_poses[3], bank_weights[3]; DevBuf<int> bank_count[3];
+	DevBuf<int> d_sel;           // [2][SEL_STRIDE]: roles for the current / next step (+ where the last result is)
+	DevBuf<int> d_mslot;         // [Pcap] sharded step: slot of every particle's mixture in the OUT bank
 	const int* d_res_slots = nullptr;   // slots of the last step's result in RESMIX (frozen mode getters)
-	int*   d_inslot = nullptr;   // [Pcap] slot of every particle's mixture in the INMIX bank (identity unless the last step resampled)
+	DevBuf<int> d_inslot;        // [Pcap] slot of every particle's mixture in the INMIX bank (identity unless the last step resampled)
 	int    parity = 0;
 	int    h_sel[SEL_STRIDE] = {0, 1, 2, 0, 0, 0, 0, 0};
 
-	double* d_z = nullptr;
-	double* d_emit_w = nullptr;  int* d_emit_idx = nullptr; double* d_emit_rec = nullptr; int* d_emit_count = nullptr;
-	int*    d_born_count = nullptr; int* d_born_k = nullptr; double* d_born_mean = nullptr;
-	double* d_alpha = nullptr; double* d_setll = nullptr;
-	int*    d_flags = nullptr; int* d_src = nullptr; int* d_info = nullptr;
-	MurtyNodes* d_murty = nullptr;
-	char* d_bigws = nullptr; unsigned long long bigws_bytes = 0; unsigned long long* d_bigws_used = nullptr;   // association slab (clusters beyond 64 rows)
-	double* d_jscratch = nullptr;
+	DevBuf<double> d_z;
+	DevBuf<double> d_emit_w; DevBuf<int> d_emit_idx; DevBuf<double> d_emit_rec; DevBuf<int> d_emit_count;
+	DevBuf<int>    d_born_count, d_born_k; DevBuf<double> d_born_mean;
+	DevBuf<double> d_alpha, d_setll;
+	int*    d_flags = nullptr; DevBuf<int> d_src; int* d_info = nullptr;   // (d_info, d_flags: words of d_sel's block)
+	DevBuf<MurtyNodes> d_murty;
+	DevBuf<char> d_bigws; unsigned long long bigws_bytes = 0; DevBuf<unsigned long long> d_bigws_used;   // association slab (clusters beyond 64 rows)
+	DevBuf<double> d_jscratch;
 	int cmcap = 0;
-	int* d_cand_count = nullptr; double* d_denom = nullptr;
-	int* d_cand = nullptr; int candcap = 0;
-	double* d_alm = nullptr; int* d_aJ = nullptr; double* d_account = nullptr;
-	double* d_stamps = nullptr;
-	double* d_srec = nullptr;
-	double* d_outw = nullptr;     // [Pcap][cap] the pruned weights as a plane (StepBufs::outw)
-	double* d_wcopy = nullptr; int* d_cover = nullptr;   // k_prune_merge -> k_alpha_density (see StepBufs)
-	double* d_motion = nullptr;   // odometry[6] + noise[P][6] of phd_update_motion
-	double* d_quasi = nullptr;    // phd_quasi_set_loglik: poses[Pcap][7], landmarks[Jcap][3], z[256][3], out[Pcap]
-	int*    h_status = nullptr;   // pinned mirror of [d_sel (two parities) | d_info | d_flags], one block on the device
-	double* h_quasi = nullptr;    // ... its pinned mirror on the host (+ one word for the flags): one stream wait per call, no pageable copies
-	double* d_gw = nullptr; int gwcap = 0;           // gathered weights of all ranks (+ their status words behind them: flagslot)
-	double* d_stage = nullptr;                       // device staging of phd_set_poses / phd_set_weights (stored into the IN bank by k_store_small)
+	DevBuf<int> d_cand_count; DevBuf<double> d_denom;
+	DevBuf<int> d_cand; int candcap = 0;
+	DevBuf<double> d_alm; DevBuf<int> d_aJ; DevBuf<double> d_account;
+	DevBuf<double> d_stamps;
+	DevBuf<double> d_srec;
+	DevBuf<double> d_outw;        // [Pcap][cap] the pruned weights as a plane (StepBufs::outw)
+	DevBuf<double> d_wcopy; DevBuf<int> d_cover;   // k_prune_merge -> k_alpha_density (see StepBufs)
+	DevBuf<double> d_motion;      // odometry[6] + noise[P][6] of phd_update_motion
+	DevBuf<double> d_quasi;       // phd_quasi_set_loglik: poses[Pcap][7], landmarks[Jcap][3], z[256][3], out[Pcap]
+	PinBuf<int>    h_status;      // pinned mirror of [d_sel (two parities) | d_info | d_flags], one block on the device
+	PinBuf<double> h_quasi;       // ... its pinned mirror on the host (+ one word for the flags): one stream wait per call, no pageable copies
+	DevBuf<double> d_gw; int gwcap = 0;              // gathered weights of all ranks (+ their status words behind them: flagslot)
+	DevBuf<double> d_stage;                          // device staging of phd_set_poses / phd_set_weights (stored into the IN bank by k_store_small)
 	// pinned host staging of the per-frame inputs (poses, weights, odometry + noise, measurements): the caller's buffers are
 	// copied here and are free when the call returns; the copy to the device is asynchronous. Two buffers, each guarded by
 	// an event recorded behind the copy that reads it.
-	double* h_stage[2] = {nullptr, nullptr}; hipEvent_t ev_stage[2] = {nullptr, nullptr}; bool stage_used[2] = {false, false};
+	PinBuf<double> h_stage[2]; Event ev_stage[2]; bool stage_used[2] = {false, false};
 	int stage_i = 0; size_t stagecap = 0;
 	// the depth map of phd_set_depth_map (KinectMeasurer): the device copy dp.depth points at (depthcap floats, grown on demand) and
 	// its own pair of pinned staging slots, guarded like h_stage (hdepthcap floats each)
-	float* d_depth = nullptr; size_t depthcap = 0;
-	float* h_depth[2] = {nullptr, nullptr}; hipEvent_t ev_depth[2] = {nullptr, nullptr}; bool depth_used[2] = {false, false};
+	DevBuf<float> d_depth; size_t depthcap = 0;
+	PinBuf<float> h_depth[2]; Event ev_depth[2]; bool depth_used[2] = {false, false};
 	int depth_i = 0; size_t hdepthcap = 0;
 	int nr_static_lds = 0;                           // static LDS of k_normalise_resample
 	// the step over a grid of workgroups (k_nr_*, phd_resample.h) for weight vectors of nr_grid_min .. 65 536 entries (environment
 	// PHD_NR_GRID_MIN; 0: never): its scratch, made on first use
-	int nr_grid_min = NR_GRID_MIN; int nrcap = 0; double* d_nrd = nullptr; int* d_nri = nullptr;
+	int nr_grid_min = NR_GRID_MIN; int nrcap = 0; DevBuf<double> d_nrd; DevBuf<int> d_nri;
 	// sharded step (one rank of a multi-GPU particle set: a process of its own, or a shard of a phd_create_multi handle)
-	double*  d_lw = nullptr;                         // [Pcap] local weights, exported for the host's all-gather (per-rank host)
-	double** d_dst_tab = nullptr; int ndst = 1;      // device table: where k_push_weights stores the local weights (own d_lw | every shard's d_gw)
+	DevBuf<double>  d_lw;                            // [Pcap] local weights, exported for the host's all-gather (per-rank host)
+	DevBuf<double*> d_dst_tab; int ndst = 1;         // device table: where k_push_weights stores the local weights (own d_lw | every shard's d_gw)
 	int      push_first = 0, push_flagslot = -1;     // ... at which offset, and where the status word goes (-1: nowhere)
-	double** d_recv_tab = nullptr;                   // device table: the receive buffer of every shard / rank (filled by phd_create_multi, phd_migration_set_peers / _ipc_open)
+	DevBuf<double*> d_recv_tab;                      // device table: the receive buffer of every shard / rank (filled by phd_create_multi, phd_migration_set_peers / _ipc_open)
 	bool peers_set = false;                          // ... it is filled: migrating particles can be pushed
 	bool gw_shared = false;                          // other shards hold the address of d_gw (multi-device handle): it cannot grow
 	const double* d_gflags = nullptr;                // the gathered status words (multi-device handle)
-	double* d_send = nullptr; double* d_recv = nullptr; int* d_plan = nullptr; int sendrecs = 0, recvrecs = 0;
-	MigPlan plan = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};   // device-resident migration plan (k_plan_migration)
+	DevBuf<double> d_send, d_recv; DevBuf<int> d_plan; int sendrecs = 0, recvrecs = 0;
+	MigPlan plan = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};   // device-resident migration plan (k_plan_migration); plain pointers as the banks, owned by:
+	DevBuf<int> plan_code, plan_fslot, plan_sendlist, plan_counts; DevBuf<long long> plan_senddst;
 	// the plan over a grid of workgroups (k_plan_count / k_plan_lists) for global vectors of plan_grid_min .. 65 536 slots whose
 	// ranks hold a multiple of 64 particles (environment PHD_PLAN_GRID_MIN; 0: never): its accumulators (two sets, alternating)
-	int plan_grid_min = PLAN_GRID_MIN; int* d_plang = nullptr; int plan_par = 0;
-	int* h_counts = nullptr; int plan_seq = 0;       // pinned + mapped: the plan's counts as the kernel writes them, and the word the host polls
+	int plan_grid_min = PLAN_GRID_MIN; DevBuf<int> d_plang; int plan_par = 0;
+	PinBuf<int> h_counts; int plan_seq = 0;          // pinned + mapped: the plan's counts as the kernel writes them, and the word the host polls
 	bool plan_waiting = false;                       // a plan kernel with host counts is in flight
 	int world = 1, rank = 0;                         // of the last global step
 	int nsend = 0, nrecv = 0, last_world_particles = 1;
@@ -158,7 +190,7 @@ struct phd_navigator {
 	unsigned long long landing_seq = 0;              // number of the last device-path global step (the flags' stamp)
 	int       landing_inline = 0;                    // 1 (PHD_LANDING_INLINE): the wait inside k_finish_sharded instead of k_wait_landing in front of it
 	long long landing_ticks = 1000000000LL;          // bound of the wait for a flag, in ticks of the 100 MHz counter: 10 s (environment PHD_LANDING_TIMEOUT_MS)
-	double* d_graw = nullptr; int grawcap = 0;       // per-rank host: the all-gather's landing buffer, [world][P + 1] (weights | status word)
+	DevBuf<double> d_graw; int grawcap = 0;          // per-rank host: the all-gather's landing buffer, [world][P + 1] (weights | status word)
 	std::vector<void*> ipc_opened;                   // peers' receive buffers opened with hipIpcOpenMemHandle (closed in phd_destroy)
 	bool plan_on_device = false;                     // the last global step left its plan on the device only (phd_step_global_device_async)
 	// host mirrors handed out by the getters
@@ -294,8 +326,6 @@ static inline void enter(phd_navigator* nav)
 	nav->pipe_ok = false;
 }
 
-int zb_of(int M) { return M <= 64 ? 1 : (M <= 128 ? 2 : 4); }
-
 // Non-finite numbers do not cross the ABI (include/phdhip.h, "Non-finite input"): the reference lets a NaN term poison a
 // whole weight sum (PHDNavigator.cs:886-890) where the device's pair loops count a NaN exponent as 0 (exp_pair); with
 // finite input the two never meet.
@@ -329,46 +359,55 @@ void stage_release(phd_navigator* nav)
 }
 
 
-// HIP events around every kernel launch, on the stream the kernel is launched on. `chained`: the launch follows the
-// previous timed launch on the same stream with nothing in between, so that launch's end event is this one's start.
-void timer_begin(phd_navigator* nav, const char* name, hipStream_t st = nullptr, bool chained = false)
-{
-	if (!st) st = nav->stream;
-	if (!nav->timing || !nav->timing_now) return;
-	if (nav->ntimers == nav->timers.size()) {
-		if (nav->timers.size() >= 65536) { nav->timing = false; return; }
-		Timer t;
-		t.name = name;
-		t.t0_from = -1;
-		// (timing only, read after a stream synchronisation: no system-scope fence when they are recorded — the fence of a default event
-		// writes the caches back in front of every timed launch and is part of what the step then costs)
-		if (hipEventCreateWithFlags(&t.t0, hipEventDisableSystemFence) != hipSuccess || hipEventCreateWithFlags(&t.t1, hipEventDisableSystemFence) != hipSuccess) {
-			(void) hipGetLastError();
-			if (hipEventCreate(&t.t0) != hipSuccess || hipEventCreate(&t.t1) != hipSuccess) { nav->timing = false; return; }
+// HIP events around every kernel launch, on the stream the kernel is launched on: the scope of a Timed is one record.
+// `chained`: the launch follows the previous timed launch on the same stream with nothing in between, so that launch's end
+// event is this one's start.
+struct Timed {
+	phd_navigator* nav;
+	hipStream_t    st;
+	Timed(phd_navigator* nav_, const char* name, hipStream_t st_, bool chained = false) : nav(nav_), st(st_)
+	{
+		if (!nav->timing || !nav->timing_now) return;
+		if (nav->ntimers == nav->timers.size()) {
+			if (nav->timers.size() >= 65536) { nav->timing = false; return; }
+			Timer t;
+			t.name = name;
+			t.t0_from = -1;
+			// (timing only, read after a stream synchronisation: no system-scope fence when they are recorded — the fence of a default event
+			// writes the caches back in front of every timed launch and is part of what the step then costs)
+			if (hipEventCreateWithFlags(&t.t0, hipEventDisableSystemFence) != hipSuccess || hipEventCreateWithFlags(&t.t1, hipEventDisableSystemFence) != hipSuccess) {
+				(void) hipGetLastError();
+				if (hipEventCreate(&t.t0) != hipSuccess || hipEventCreate(&t.t1) != hipSuccess) { nav->timing = false; return; }
+			}
+			nav->timers.push_back(t);
 		}
-		nav->timers.push_back(t);
+		Timer& t = nav->timers[nav->ntimers];
+		t.name = name;
+		t.t0_from = (chained && nav->ntimers > 0) ? (int) nav->ntimers - 1 : -1;
+		if (t.t0_from < 0) hipEventRecord(t.t0, st);
 	}
-	Timer& t = nav->timers[nav->ntimers];
-	t.name = name;
-	t.t0_from = (chained && nav->ntimers > 0) ? (int) nav->ntimers - 1 : -1;
-	if (t.t0_from < 0) hipEventRecord(t.t0, st);
-}
+	~Timed()
+	{
+		if (!nav->timing || !nav->timing_now || nav->ntimers >= nav->timers.size()) return;
+		hipEventRecord(nav->timers[nav->ntimers].t1, st);
+		nav->ntimers++;
+	}
+	Timed(const Timed&) = delete;
+	Timed& operator=(const Timed&) = delete;
+};
 
-void timer_end(phd_navigator* nav, const char* name, hipStream_t st = nullptr)
+// one kernel launch as one record
+template <class... KA, class... A>
+void launch_timed(phd_navigator* nav, const char* name, hipStream_t st, bool chained, void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds, const A&... args)
 {
-	if (!st) st = nav->stream;
-	if (!nav->timing || !nav->timing_now || nav->ntimers >= nav->timers.size()) return;
-	hipEventRecord(nav->timers[nav->ntimers].t1, st);
-	nav->ntimers++;
+	Timed t(nav, name, st, chained);
+	hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
 }
 
 const char* T_SW = "k_sweep";
 const char* T_EF = "k_emit_finish";
 const char* T_PM = "k_prune_merge";
 const char* T_EP = "k_emit_prune";
-#ifdef PHD_WITH_FUSE_SEP
-const char* T_SEP = "k_sweep_emit_prune";
-#endif
 const char* T_WA = "k_alpha_assoc";
 const char* T_WD = "k_alpha_density";
 const char* T_NR = "k_normalise_resample";
@@ -378,24 +417,70 @@ const char* T_PK = "k_pack_particles";
 const char* T_PW = "k_push_weights";
 const char* T_CH = "k_particle_chain";
 
+// The per-particle kernels of a step are compiled per measurement-block count ZB (64 measurements a block), for up to 32
+// measurements with the sweep that takes two components per visit (HALF, phd_sweep.h; one block only), and with the Kinect
+// detection probability of a depth map (DEPTH, phd_device.h). One row per build: its kernels and the dynamic LDS each asks
+// for at a handle's max_quantity. (k_quasi_setll / _grad have no HALF or DEPTH build: every row of a ZB names the same two.)
+struct StepVariant {
+	int  zb;
+	bool half, depth;
+	void (*chain)(DevParams, StepBufs, int, int);
+	void (*sweep)(DevParams, StepBufs);
+	void (*emit_prune)(DevParams, StepBufs, int);
+	void (*emit_finish)(DevParams, StepBufs);
+	void (*assoc)(DevParams, StepBufs, int);
+	void (*assoc_main)(DevParams, StepBufs, int);
+	void (*density_big)(DevParams, StepBufs, int, int);
+	void (*quasi)(DevParams, StepBufs, int);
+	void (*quasi_grad)(DevParams, StepBufs, int);
+	int  (*chain_pool)(int);
+	int zi() const { return zb >> 1; }   // index of ZB = 1, 2, 4 (phd_navigator::chain_ok)
+	int chain_lds(int cutcap) const { return chain_pool(cutcap); }
+	int assoc_lds(int cutcap) const { return alpha_lds(zb * 64, cutcap).bytes; }
+	int density_big_lds(int cutcap) const { return std::max(assoc_lds(cutcap), (int) (DENS_LDS_DOUBLES * 8)); }   // the larger of the two bodies' pools
+	static int emit_prune_lds(int cutcap) { return std::max((int) prune_lds(cutcap).bytes, (int) (EMIT_LDS_DOUBLES * 8)); }
+};
+
+template <int ZB, bool HALF, bool DEPTH>
+StepVariant make_variant()
+{
+	return {ZB, HALF, DEPTH, k_particle_chain<ZB, HALF, DEPTH>, k_sweep<ZB, HALF, DEPTH>, k_emit_prune<DEPTH>, k_emit_finish<DEPTH>, k_alpha_assoc<ZB, DEPTH>,
+	        k_alpha_assoc_main<ZB, DEPTH>, k_alpha_density_big<ZB, DEPTH>, k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, chain_lds_bytes<ZB>};
+}
+
+const StepVariant step_variants[8] = {make_variant<1, false, false>(), make_variant<1, true, false>(), make_variant<2, false, false>(), make_variant<4, false, false>(),
+                                      make_variant<1, false, true>(),  make_variant<1, true, true>(),  make_variant<2, false, true>(),  make_variant<4, false, true>()};
+
+int zb_of(int M) { return M <= 64 ? 1 : (M <= 128 ? 2 : 4); }
+
+// The build that serves a step of M measurements, with or without a depth map: the one statement of that rule.
+const StepVariant& variant(int M, bool depth_set)
+{
+	const int zb = zb_of(M);
+	const bool half = zb == 1 && M <= 32;
+	for (const StepVariant& v : step_variants) {
+		if (v.zb == zb && v.half == half && v.depth == depth_set) return v;
+	}
+	return step_variants[0];   // (not reached: the table holds every combination the rule yields)
+}
+
 // The per-particle kernels of a step. With nsplit > 1 the particle range is cut into sub-ranges whose kernel
 // chains run on concurrent streams (forked from and joined back into the handle's stream), so that the
 // latency-bound kernels of one sub-range overlap the arithmetic-bound kernels of another.
 // `pipe` >= 0 (phd_step_async, two sub-ranges): no fork and no join here — the caller has ordered the streams and ends the step on
 // the stream that finishes last, `pipe` (0 `stream`, 1 aux[0]); the other one's chain is enqueued first.
-template <int ZB, bool DEPTH>
-int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, int pipe = -1)
+int launch_map(phd_navigator* nav, const StepBufs& b0, bool with_alpha, int pipe = -1)
 {
-	const int P = nav->P;
+	const StepVariant& v = variant(nav->M, nav->dp.depth != nullptr);
+	const int P = nav->P, cutcap = nav->cutcap;
 	// two half-ranges measured best at 2048 particles (1.10 -> 1.02 ms); below ~4 workgroups per CU and sub-range it does not pay
 	const int want = nav->nsplit > 0 ? nav->nsplit : (P >= 1024 ? 2 : 1);
 	const int S = std::max(1, std::min(std::min(want, (int) phd_navigator::MAXSPLIT), P));
-	const size_t lp = (size_t) prune_lds(nav->cutcap).bytes;
-	const AlphaLds lay = alpha_lds(ZB * 64, nav->cutcap);   // (the dynamic LDS limits of the kernels were raised once, in phd_create)
-	const int zi = ZB == 1 ? 0 : (ZB == 2 ? 1 : 2);
-	if (nav->chain_ok[zi] && P <= nav->chain_max) {
+	const size_t lp = (size_t) prune_lds(cutcap).bytes;   // (the dynamic LDS limits of the kernels were raised once, in phd_create)
+	const dim3 block(256);
+	const int wa = with_alpha ? 1 : 0;
+	if (nav->chain_ok[v.zi()] && P <= nav->chain_max) {
 		// a small particle set (up to two workgroups per CU): the whole per-particle chain as one launch
-		timer_begin(nav, T_CH);
 		// (a helper workgroup per particle for the densities when all 2 P workgroups can be on the chip together; the results are the
 		// same bits whether a helper comes in time or not: k_particle_chain)
 		StepBufs bc = b0;
@@ -407,11 +492,7 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 			}
 			bc.dsplit = nav->dsplit_late > 0 ? 1 + nav->dsplit_late : 1; bc.dstamp = nav->dseq;
 		}
-		const int G = helpers ? 2 * P : P;
-		// (up to 32 measurements: the sweep with two components per visit, phd_sweep.h HALF)
-		if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_particle_chain<1, true, DEPTH>), dim3(G), dim3(256), (size_t) chain_lds_bytes<1>(nav->cutcap), nav->stream, nav->dp, bc, nav->cutcap, with_alpha ? 1 : 0);
-		else hipLaunchKernelGGL((k_particle_chain<ZB, false, DEPTH>), dim3(G), dim3(256), (size_t) chain_lds_bytes<ZB>(nav->cutcap), nav->stream, nav->dp, bc, nav->cutcap, with_alpha ? 1 : 0);
-		timer_end(nav, T_CH);
+		launch_timed(nav, T_CH, nav->stream, false, v.chain, dim3(helpers ? 2 * P : P), block, (size_t) v.chain_lds(cutcap), nav->dp, bc, cutcap, wa);
 		HC(hipGetLastError());
 		nav->last_defer = 0;
 		return PHD_OK;
@@ -422,7 +503,7 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 	}
 	const bool defer = with_alpha && nav->defer_big != 0;
 	nav->last_defer = defer ? 1 : 0;
-	const size_t ldb = std::max((size_t) lay.bytes, (size_t) DENS_LDS_DOUBLES * 8);   // k_alpha_density_big: the larger of the two bodies' pools
+	const size_t la = (size_t) v.assoc_lds(cutcap);
 	for (int si = 0; si < S; si++) {
 		const int s = (pipe >= 0 && S == 2) ? (si == 0 ? 1 - pipe : pipe) : si;
 		StepBufs b = b0;
@@ -431,53 +512,25 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 		b.p0 = (int) ((long long) P * s / S);
 		const int n = (int) ((long long) P * (s + 1) / S) - b.p0;
 		if (n <= 0) continue;
-		hipStream_t st = s == 0 ? nav->stream : nav->aux[s - 1];
-#ifdef PHD_WITH_FUSE_SEP
-		if (nav->fuse_sep) {
-			const size_t ld3 = std::max(std::max(lp, (size_t) EMIT_LDS_DOUBLES * 8), (size_t) SweepLds<ZB>::doubles * 8);
-			timer_begin(nav, T_SEP, st);
-			if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_sweep_emit_prune<1, true, DEPTH>), dim3(n), dim3(256), ld3, st, nav->dp, b, nav->cutcap);
-			else hipLaunchKernelGGL((k_sweep_emit_prune<ZB, false, DEPTH>), dim3(n), dim3(256), ld3, st, nav->dp, b, nav->cutcap);
-			timer_end(nav, T_SEP, st);
-		}
-		else
-#endif
-		{
-		timer_begin(nav, T_SW, st);
-		if (ZB == 1 && nav->M <= 32) hipLaunchKernelGGL((k_sweep<1, true, DEPTH>), dim3(n), dim3(256), 0, st, nav->dp, b);
-		else hipLaunchKernelGGL((k_sweep<ZB, false, DEPTH>), dim3(n), dim3(256), 0, st, nav->dp, b);
-		timer_end(nav, T_SW, st);
-		if (nav->fuse_ep < 0 ? ZB == 1 : nav->fuse_ep != 0) {
-			timer_begin(nav, T_EP, st, true);
-			hipLaunchKernelGGL(k_emit_prune<DEPTH>, dim3(n), dim3(256), std::max(lp, (size_t) EMIT_LDS_DOUBLES * 8), st, nav->dp, b, nav->cutcap);
-			timer_end(nav, T_EP, st);
+		hipStream_t st = s == 0 ? nav->stream : (hipStream_t) nav->aux[s - 1];
+		const dim3 grid(n);
+		launch_timed(nav, T_SW, st, false, v.sweep, grid, block, 0, nav->dp, b);
+		if (nav->fuse_ep < 0 ? v.zb == 1 : nav->fuse_ep != 0) {
+			launch_timed(nav, T_EP, st, true, v.emit_prune, grid, block, (size_t) v.emit_prune_lds(cutcap), nav->dp, b, cutcap);
 		}
 		else {
-			timer_begin(nav, T_EF, st, true);
-			hipLaunchKernelGGL(k_emit_finish<DEPTH>, dim3(n), dim3(256), 0, st, nav->dp, b);
-			timer_end(nav, T_EF, st);
-			timer_begin(nav, T_PM, st, true);
-			hipLaunchKernelGGL(k_prune_merge, dim3(n), dim3(256), lp, st, nav->dp, b, nav->cutcap);
-			timer_end(nav, T_PM, st);
-		}
+			launch_timed(nav, T_EF, st, true, v.emit_finish, grid, block, 0, nav->dp, b);
+			launch_timed(nav, T_PM, st, true, k_prune_merge, grid, block, lp, nav->dp, b, cutcap);
 		}
 		if (with_alpha && defer) {
-			timer_begin(nav, T_WA, st, true);
-			hipLaunchKernelGGL((k_alpha_assoc_main<ZB, DEPTH>), dim3(n), dim3(256), lay.bytes, st, nav->dp, b, nav->cutcap);
-			timer_end(nav, T_WA, st);
+			launch_timed(nav, T_WA, st, true, v.assoc_main, grid, block, la, nav->dp, b, cutcap);
 			// the particles it listed are worked off by the first workgroups of the densities' launch
 			const int nbig = std::max(1, std::min(nav->nbig, n));
-			timer_begin(nav, T_WD, st, true);
-			hipLaunchKernelGGL((k_alpha_density_big<ZB, DEPTH>), dim3(n + nbig), dim3(256), ldb, st, nav->dp, b, nav->cutcap, nbig);
-			timer_end(nav, T_WD, st);
+			launch_timed(nav, T_WD, st, true, v.density_big, dim3(n + nbig), block, (size_t) v.density_big_lds(cutcap), nav->dp, b, cutcap, nbig);
 		}
 		else if (with_alpha) {
-			timer_begin(nav, T_WA, st, true);
-			hipLaunchKernelGGL((k_alpha_assoc<ZB, DEPTH>), dim3(n), dim3(256), lay.bytes, st, nav->dp, b, nav->cutcap);
-			timer_end(nav, T_WA, st);
-			timer_begin(nav, T_WD, st, true);
-			hipLaunchKernelGGL(k_alpha_density, dim3(n), dim3(256), 0, st, nav->dp, b);
-			timer_end(nav, T_WD, st);
+			launch_timed(nav, T_WA, st, true, v.assoc, grid, block, la, nav->dp, b, cutcap);
+			launch_timed(nav, T_WD, st, true, k_alpha_density, grid, block, 0, nav->dp, b);
 		}
 	}
 	for (int s = 1; s < S && pipe < 0; s++) {
@@ -490,35 +543,12 @@ int launch_map_kernels(phd_navigator* nav, const StepBufs& b0, bool with_alpha, 
 
 // PHDNavigator.QuasiSetLogLikelihood (PHDNavigator.cs:526-531) for a batch of candidate poses against one landmark
 // set and one measurement set: one workgroup per pose through the association kernel's own code.
-template <int ZB>
 int launch_quasi(phd_navigator* nav, const StepBufs& b, int nposes, bool gradient)
 {
-	const AlphaLds lay = alpha_lds(ZB * 64, nav->cutcap);
-	if (gradient) {
-		hipLaunchKernelGGL(k_quasi_setll_grad<ZB>, dim3(nposes), dim3(256), lay.bytes, nav->stream, nav->dp, b, nav->cutcap);
-	}
-	else {
-		hipLaunchKernelGGL(k_quasi_setll<ZB>, dim3(nposes), dim3(256), lay.bytes, nav->stream, nav->dp, b, nav->cutcap);
-	}
+	const StepVariant& v = variant(b.M, false);
+	hipLaunchKernelGGL(gradient ? v.quasi_grad : v.quasi, dim3(nposes), dim3(256), (size_t) v.assoc_lds(nav->cutcap), nav->stream, nav->dp, b, nav->cutcap);
 	HC(hipGetLastError());
 	return PHD_OK;
-}
-
-int launch_map(phd_navigator* nav, const StepBufs& b, bool with_alpha, int pipe = -1)
-{
-	// (a depth map set: the kernels compiled with the Kinect detection probability, phd_device.h)
-	if (nav->dp.depth) {
-		switch (zb_of(nav->M)) {
-		case 1:  return launch_map_kernels<1, true>(nav, b, with_alpha, pipe);
-		case 2:  return launch_map_kernels<2, true>(nav, b, with_alpha, pipe);
-		default: return launch_map_kernels<4, true>(nav, b, with_alpha, pipe);
-		}
-	}
-	switch (zb_of(nav->M)) {
-	case 1:  return launch_map_kernels<1, false>(nav, b, with_alpha, pipe);
-	case 2:  return launch_map_kernels<2, false>(nav, b, with_alpha, pipe);
-	default: return launch_map_kernels<4, false>(nav, b, with_alpha, pipe);
-	}
 }
 
 // graw / Pl / world (per-rank host): the weights still lie as the all-gather delivered them, [rank][Pl + 1]; the first launch un-gathers them
@@ -532,11 +562,11 @@ int launch_normalise(phd_navigator* nav, const StepBufs& b, double* gw, int P, d
 		// one particle per thread over a grid, four launches (phd_resample.h, "over a GRID"): 16 384 weights in ~15 us instead of 48
 		if (P > nav->nrcap) {
 			HC(hipDeviceSynchronize());   // (first use, or a longer vector than ever before: rare)
-			hipFree(nav->d_nrd); hipFree(nav->d_nri);
-			nav->d_nrd = nullptr; nav->d_nri = nullptr; nav->nrcap = 0;
+			nav->d_nrd.reset(); nav->d_nri.reset();
+			nav->nrcap = 0;
 			const int Gc = (P + 255) / 256;
-			HC(hipMalloc((void**) &nav->d_nrd, ((size_t) Gc * (NR_STAT + NR_SLOT) + 2 * (size_t) P) * 8));
-			HC(hipMalloc((void**) &nav->d_nri, ((size_t) P + 4) * 4));
+			HC(nav->d_nrd.alloc((size_t) Gc * (NR_STAT + NR_SLOT) + 2 * (size_t) P));
+			HC(nav->d_nri.alloc((size_t) P + 4));
 			nav->nrcap = P;
 		}
 		NrGrid nr;
@@ -796,8 +826,11 @@ phd_navigator* phd_create(const phd_params* params, int device)
 	nav->Jcap = std::min(1024, (nav->cutcap + 63) & ~63);
 	nav->P = 0;
 
-	auto dalloc = [&](void** ptr, size_t bytes) { return hipMalloc(ptr, std::max<size_t>(bytes, 16)) == hipSuccess; };
-	bool ok = hipStreamCreateWithFlags(&nav->own_stream, hipStreamNonBlocking) == hipSuccess;
+	auto dalloc = [](auto& buf, size_t bytes) {   // (at least 16 bytes; every size here is a whole number of the buffer's elements)
+		const size_t el = sizeof(typename std::remove_reference_t<decltype(buf)>::element);
+		return buf.alloc((std::max<size_t>(bytes, 16) + el - 1) / el) == hipSuccess;
+	};
+	bool ok = hipStreamCreateWithFlags(nav->own_stream.put(), hipStreamNonBlocking) == hipSuccess;
 	nav->stream = nav->own_stream;
 	// The events that order the sub-range streams among themselves (same device, never inspected by the host): recorded without
 	// the system-scope fence a default event performs (5 us per step boundary; the kernels' own release / acquire at their ends
@@ -815,22 +848,19 @@ phd_navigator* phd_create(const phd_params* params, int device)
 		return hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
 	};
 	for (int i = 0; i < phd_navigator::MAXSPLIT - 1; i++) {
-		ok = ok && hipStreamCreateWithFlags(&nav->aux[i], hipStreamNonBlocking) == hipSuccess;
-		ok = ok && ev_create(&nav->ev_join[i], evflags);
+		ok = ok && hipStreamCreateWithFlags(nav->aux[i].put(), hipStreamNonBlocking) == hipSuccess;
+		ok = ok && ev_create(nav->ev_join[i].put(), evflags);
 	}
 	// ev_fork keeps the default (system-scope) release: it is recorded exactly when something ELSE preceded the step on the
 	// handle's stream — typically the host-to-device copy of phd_set_measurements — and is then the only link between that copy
 	// and the aux stream's k_sweep. It is off the back-to-back path (phd_step_async behind phd_step_async records no fork), so its
 	// 5 us do not touch the steady state.
-	ok = ok && ev_create(&nav->ev_fork, hipEventDisableTiming);
-	ok = ok && ev_create(&nav->ev_res, evflags);
+	ok = ok && ev_create(nav->ev_fork.put(), hipEventDisableTiming);
+	ok = ok && ev_create(nav->ev_res.put(), evflags);
 	if (const char* e = getenv("PHD_PIPELINE")) nav->pipeline = atoi(e) != 0;
 	if (const char* e = getenv("PHD_DEVICE_ORDER")) nav->device_order = atoi(e) != 0;
 	if (const char* e = getenv("PHD_DEFER_BIG")) nav->defer_big = atoi(e) != 0;
 	if (const char* e = getenv("PHD_FUSE_EP")) nav->fuse_ep = atoi(e) != 0 ? 1 : 0;
-#ifdef PHD_WITH_FUSE_SEP
-	if (const char* e = getenv("PHD_FUSE_SEP")) nav->fuse_sep = atoi(e) != 0 ? 1 : 0;
-#endif
 	if (const char* e = getenv("PHD_NBIG")) nav->nbig = std::max(1, atoi(e));
 	if (const char* e = getenv("PHD_SPLIT")) nav->nsplit = std::max(0, atoi(e));
 	if (const char* e = getenv("PHD_CHAIN_MAX")) nav->chain_max = std::max(0, atoi(e));
@@ -842,10 +872,11 @@ phd_navigator* phd_create(const phd_params* params, int device)
 	if (const char* e = getenv("PHD_PLAN_GRID_MIN")) nav->plan_grid_min = std::max(0, atoi(e));
 	size_t plane = (size_t) nav->Pcap * nav->cap;
 	for (int i = 0; i < 3 && ok; i++) {
-		ok = ok && dalloc((void**) &nav->bank[i].mix, plane * MIX_REC * 8);
-		ok = ok && dalloc((void**) &nav->bank[i].count, (size_t) nav->Pcap * 4);
-		ok = ok && dalloc((void**) &nav->bank[i].poses, (size_t) nav->Pcap * 7 * 8);
-		ok = ok && dalloc((void**) &nav->bank[i].weights, (size_t) nav->Pcap * 8);
+		ok = ok && dalloc(nav->bank_mix[i], plane * MIX_REC * 8);
+		ok = ok && dalloc(nav->bank_count[i], (size_t) nav->Pcap * 4);
+		ok = ok && dalloc(nav->bank_poses[i], (size_t) nav->Pcap * 7 * 8);
+		ok = ok && dalloc(nav->bank_weights[i], (size_t) nav->Pcap * 8);
+		nav->bank[i] = Bank{nav->bank_mix[i], nav->bank_count[i], nav->bank_poses[i], nav->bank_weights[i]};
 		if (ok) {
 			hipMemset(nav->bank[i].count, 0, (size_t) nav->Pcap * 4);
 			hipMemset(nav->bank[i].weights, 0, (size_t) nav->Pcap * 8);
@@ -855,131 +886,88 @@ phd_navigator* phd_create(const phd_params* params, int device)
 	size_t E = (size_t) nav->Pcap * nav->ecap;
 	// the role tables (two parities), the step's info words and its flag word in ONE block: phd_sync reads it with one copy
 	// queued on the stream it then waits for (three blocking copies before: 40 us of a 90 us step at config A)
-	ok = ok && dalloc((void**) &nav->d_sel, (2 * SEL_STRIDE + 4) * 4) && dalloc((void**) &nav->d_inslot, (size_t) nav->Pcap * 4);
+	ok = ok && dalloc(nav->d_sel, (2 * SEL_STRIDE + 4) * 4) && dalloc(nav->d_inslot, (size_t) nav->Pcap * 4);
 	if (ok) { nav->d_info = nav->d_sel + 2 * SEL_STRIDE; nav->d_flags = nav->d_info + 2; }
-	ok = ok && hipHostMalloc((void**) &nav->h_status, (2 * SEL_STRIDE + 4) * 4, hipHostMallocDefault) == hipSuccess;
-	ok = ok && dalloc((void**) &nav->d_z, (size_t) nav->Mcap * 3 * 8);
-	ok = ok && dalloc((void**) &nav->d_emit_w, E * 8) && dalloc((void**) &nav->d_emit_idx, E * 4);
-	ok = ok && dalloc((void**) &nav->d_emit_rec, E * MIX_REC * 8) && dalloc((void**) &nav->d_emit_count, (size_t) nav->Pcap * 4);
-	ok = ok && dalloc((void**) &nav->d_born_count, (size_t) nav->Pcap * 4);
-	ok = ok && dalloc((void**) &nav->d_born_k, (size_t) nav->Pcap * nav->Mcap * 4);
-	ok = ok && dalloc((void**) &nav->d_born_mean, (size_t) nav->Pcap * nav->Mcap * 3 * 8);
-	ok = ok && dalloc((void**) &nav->d_alpha, (size_t) nav->Pcap * 8) && dalloc((void**) &nav->d_setll, (size_t) nav->Pcap * 8);
-	ok = ok && dalloc((void**) &nav->d_src, (size_t) nav->Pcap * 4);
-	ok = ok && dalloc((void**) &nav->d_murty, (size_t) nav->Pcap * sizeof(MurtyNodes));
+	ok = ok && nav->h_status.alloc(2 * SEL_STRIDE + 4, hipHostMallocDefault) == hipSuccess;
+	ok = ok && dalloc(nav->d_z, (size_t) nav->Mcap * 3 * 8);
+	ok = ok && dalloc(nav->d_emit_w, E * 8) && dalloc(nav->d_emit_idx, E * 4);
+	ok = ok && dalloc(nav->d_emit_rec, E * MIX_REC * 8) && dalloc(nav->d_emit_count, (size_t) nav->Pcap * 4);
+	ok = ok && dalloc(nav->d_born_count, (size_t) nav->Pcap * 4);
+	ok = ok && dalloc(nav->d_born_k, (size_t) nav->Pcap * nav->Mcap * 4);
+	ok = ok && dalloc(nav->d_born_mean, (size_t) nav->Pcap * nav->Mcap * 3 * 8);
+	ok = ok && dalloc(nav->d_alpha, (size_t) nav->Pcap * 8) && dalloc(nav->d_setll, (size_t) nav->Pcap * 8);
+	ok = ok && dalloc(nav->d_src, (size_t) nav->Pcap * 4);
+	ok = ok && dalloc(nav->d_murty, (size_t) nav->Pcap * sizeof(MurtyNodes));
 	nav->bigws_bytes = 128ull << 20;
-	ok = ok && dalloc((void**) &nav->d_bigws, nav->bigws_bytes) && dalloc((void**) &nav->d_bigws_used, 32);   // [0] the slab's bump counter; 32-bit words behind it: the device order's ticket counter (never reset) and step number, the chain's own ticket
+	ok = ok && dalloc(nav->d_bigws, nav->bigws_bytes) && dalloc(nav->d_bigws_used, 32);   // [0] the slab's bump counter; 32-bit words behind it: the device order's ticket counter (never reset) and step number, the chain's own ticket
 	if (ok) hipMemset(nav->d_bigws_used, 0, 32);
 	nav->cmcap = nav->cap + nav->Mcap;
-	ok = ok && dalloc((void**) &nav->d_cand_count, (size_t) nav->Pcap * 4 * 4) && dalloc((void**) &nav->d_denom, (size_t) nav->Pcap * nav->Mcap * 8);
+	ok = ok && dalloc(nav->d_cand_count, (size_t) nav->Pcap * 4 * 4) && dalloc(nav->d_denom, (size_t) nav->Pcap * nav->Mcap * 8);
 	nav->candcap = 16 * nav->cmcap;   // a quarter of all pairs at 64 measurements (four wave segments); beyond it the full second sweep runs
-	ok = ok && dalloc((void**) &nav->d_cand, (size_t) nav->Pcap * nav->candcap * 8);
+	ok = ok && dalloc(nav->d_cand, (size_t) nav->Pcap * nav->candcap * 8);
 #ifdef PHD_STAMPS
-	ok = ok && dalloc((void**) &nav->d_stamps, (size_t) nav->Pcap * 16 * 8);
+	ok = ok && dalloc(nav->d_stamps, (size_t) nav->Pcap * 16 * 8);
 #endif
-	ok = ok && dalloc((void**) &nav->d_srec, (size_t) nav->Pcap * PRUNE_ROW * nav->cutcap * 8);
-	ok = ok && dalloc((void**) &nav->d_outw, plane * 8);
-	ok = ok && dalloc((void**) &nav->d_biglist, (size_t) phd_navigator::MAXSPLIT * (nav->Pcap + 2) * 4) && dalloc((void**) &nav->d_ratio, (size_t) nav->Pcap * 8);
+	ok = ok && dalloc(nav->d_srec, (size_t) nav->Pcap * PRUNE_ROW * nav->cutcap * 8);
+	ok = ok && dalloc(nav->d_outw, plane * 8);
+	ok = ok && dalloc(nav->d_biglist, (size_t) phd_navigator::MAXSPLIT * (nav->Pcap + 2) * 4) && dalloc(nav->d_ratio, (size_t) nav->Pcap * 8);
 	if (ok) hipMemset(nav->d_biglist, 0, (size_t) phd_navigator::MAXSPLIT * (nav->Pcap + 2) * 4);
-	ok = ok && dalloc((void**) &nav->d_wcopy, (size_t) nav->Pcap * (nav->cap + nav->Mcap) * 8) && dalloc((void**) &nav->d_cover, (size_t) nav->Pcap * nav->cap * 4);
-	ok = ok && dalloc((void**) &nav->d_alm, (size_t) nav->Pcap * 3 * nav->Jcap * 8);
-	ok = ok && dalloc((void**) &nav->d_aJ, (size_t) nav->Pcap * 4) && dalloc((void**) &nav->d_account, (size_t) nav->Pcap * 8);
+	ok = ok && dalloc(nav->d_wcopy, (size_t) nav->Pcap * (nav->cap + nav->Mcap) * 8) && dalloc(nav->d_cover, (size_t) nav->Pcap * nav->cap * 4);
+	ok = ok && dalloc(nav->d_alm, (size_t) nav->Pcap * 3 * nav->Jcap * 8);
+	ok = ok && dalloc(nav->d_aJ, (size_t) nav->Pcap * 4) && dalloc(nav->d_account, (size_t) nav->Pcap * 8);
 	if (nav->dsplit_max > 0) {
 		const size_t rows = (size_t) std::min(nav->Pcap, (int) DSPLIT_ROWS);
-		ok = ok && dalloc((void**) &nav->d_dsync, rows * 3 * 4);
+		ok = ok && dalloc(nav->d_dsync, rows * 3 * 4);
 		ok = ok && hipMemset(nav->d_dsync, 0, rows * 3 * 4) == hipSuccess;
 	}
-	ok = ok && dalloc((void**) &nav->d_jscratch, (size_t) nav->Pcap * alpha_jscratch_doubles(nav->Jcap) * 8);
+	ok = ok && dalloc(nav->d_jscratch, (size_t) nav->Pcap * alpha_jscratch_doubles(nav->Jcap) * 8);
 	nav->stagecap = std::max((size_t) nav->Pcap * 8 + 8, (size_t) 256 * 3);   // poses + weights | odometry + noise | measurements
-	ok = ok && dalloc((void**) &nav->d_stage, nav->stagecap * 8) && dalloc((void**) &nav->d_motion, ((size_t) nav->Pcap * 6 + 6) * 8);
+	ok = ok && dalloc(nav->d_stage, nav->stagecap * 8) && dalloc(nav->d_motion, ((size_t) nav->Pcap * 6 + 6) * 8);
 	for (int i = 0; i < 2; i++) {
-		ok = ok && hipHostMalloc((void**) &nav->h_stage[i], nav->stagecap * 8, hipHostMallocDefault) == hipSuccess;
-		ok = ok && hipEventCreateWithFlags(&nav->ev_stage[i], hipEventDisableTiming) == hipSuccess;
+		ok = ok && nav->h_stage[i].alloc(nav->stagecap, hipHostMallocDefault) == hipSuccess;
+		ok = ok && hipEventCreateWithFlags(nav->ev_stage[i].put(), hipEventDisableTiming) == hipSuccess;
 	}
 	{
 		// dynamic LDS limits, set when a handle is created: they depend on the handle's capacities only. The attribute belongs
 		// to the function ON THE CURRENT DEVICE, and the same kernels serve every handle of the process there: per device
 		// the limit is only ever raised.
-		struct DevLimits { int prune = 0, alpha[3] = {0, 0, 0}, chain[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
+		struct DevLimits { int prune = 0, alpha[8] = {0, 0, 0, 0, 0, 0, 0, 0}, chain[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };   // (per row of step_variants)
 		static DevLimits limits[PHD_MAX_DEVICES];
 		static std::mutex limits_mu;   // (handles may be created from several host threads, one per GPU)
 		std::lock_guard<std::mutex> limits_guard(limits_mu);
 		DevLimits& lim = limits[device];
-		const int lp = prune_lds(nav->cutcap).bytes;
-		if (lp > lim.prune) {
-			ok = ok && hipFuncSetAttribute((const void*) k_prune_merge, hipFuncAttributeMaxDynamicSharedMemorySize, lp) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_emit_prune<false>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lp, (int) (EMIT_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_emit_prune<true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lp, (int) (EMIT_LDS_DOUBLES * 8))) == hipSuccess;
-#ifdef PHD_WITH_FUSE_SEP
-			const int l3[3] = {std::max(lp, (int) (SweepLds<1>::doubles * 8)), std::max(lp, (int) (SweepLds<2>::doubles * 8)), std::max(lp, (int) (SweepLds<4>::doubles * 8))};
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<2>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<4>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[2]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_sweep_emit_prune<4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l3[2]) == hipSuccess;
-#endif
-			lim.prune = lp;
-		}
-		const int la[3] = {alpha_lds(64, nav->cutcap).bytes, alpha_lds(128, nav->cutcap).bytes, alpha_lds(256, nav->cutcap).bytes};
-		if (la[0] > lim.alpha[0]) {
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<1>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[0], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[0], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll_grad<1>, hipFuncAttributeMaxDynamicSharedMemorySize, la[0]) == hipSuccess;
-			lim.alpha[0] = la[0];
-		}
-		if (la[1] > lim.alpha[1]) {
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<2>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[1], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[1], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll_grad<2>, hipFuncAttributeMaxDynamicSharedMemorySize, la[1]) == hipSuccess;
-			lim.alpha[1] = la[1];
-		}
-		if (la[2] > lim.alpha[2]) {
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_assoc_main<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<4>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[2], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_alpha_density_big<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(la[2], (int) (DENS_LDS_DOUBLES * 8))) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
-			ok = ok && hipFuncSetAttribute((const void*) k_quasi_setll_grad<4>, hipFuncAttributeMaxDynamicSharedMemorySize, la[2]) == hipSuccess;
-			lim.alpha[2] = la[2];
-		}
-		// the one-launch chain: its bodies share one pool, the largest of their layouts, which must fit a workgroup (160 KB)
-		// with the kernel's few static words; where it does not (a large MaxQuantity) the separate kernels run
-		const int lc[3] = {chain_lds_bytes<1>(nav->cutcap), chain_lds_bytes<2>(nav->cutcap), chain_lds_bytes<4>(nav->cutcap)};
-		// (entries 4..7: the same kernels compiled for a depth map, phd_set_depth_map; the chain runs only where both fit)
-		const void* chainfn[8] = {(const void*) k_particle_chain<1>, (const void*) k_particle_chain<2>, (const void*) k_particle_chain<4>,
-		                          (const void*) k_particle_chain<1, true>,
-		                          (const void*) k_particle_chain<1, false, true>, (const void*) k_particle_chain<2, false, true>,
-		                          (const void*) k_particle_chain<4, false, true>, (const void*) k_particle_chain<1, true, true>};
-		bool fits[8] = {false, false, false, false, false, false, false, false};
-		for (int z = 0; z < 8 && ok; z++) {
-			const int zl = (z & 3) == 3 ? 0 : (z & 3);   // (the HALF build of the one-block chain shares its layout)
-			hipFuncAttributes fc;
-			if (hipFuncGetAttributes(&fc, chainfn[z]) != hipSuccess) { ok = false; break; }
-			if ((size_t) fc.sharedSizeBytes + (size_t) lc[zl] + 256 > 160 * 1024) continue;
-			if (lc[zl] > lim.chain[z]) {
-				if (hipFuncSetAttribute(chainfn[z], hipFuncAttributeMaxDynamicSharedMemorySize, lc[zl]) != hipSuccess) { (void) hipGetLastError(); continue; }
-				lim.chain[z] = lc[zl];
+		auto raise = [&](auto kernel, int bytes) { ok = ok && hipFuncSetAttribute((const void*) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess; };
+		const int cutcap = nav->cutcap, lp = prune_lds(cutcap).bytes;
+		const bool raise_prune = lp > lim.prune;
+		if (raise_prune) raise(k_prune_merge, lp);
+		for (int z = 0; z < 3; z++) nav->chain_ok[z] = true;
+		for (int i = 0; i < 8; i++) {
+			const StepVariant& v = step_variants[i];
+			if (raise_prune) raise(v.emit_prune, v.emit_prune_lds(cutcap));
+			const int la = v.assoc_lds(cutcap);
+			if (la > lim.alpha[i]) {
+				raise(v.assoc, la);
+				raise(v.assoc_main, la);
+				raise(v.density_big, v.density_big_lds(cutcap));
+				raise(v.quasi, la);
+				raise(v.quasi_grad, la);
+				lim.alpha[i] = la;
 			}
-			fits[z] = true;
+			// the one-launch chain: its bodies share one pool, the largest of their layouts, which must fit a workgroup (160 KB)
+			// with the kernel's few static words; where it does not (a large MaxQuantity) the separate kernels run. A step runs
+			// the chain only where every build it could pick at its ZB fits (with and without a depth map, HALF or not).
+			const int lc = v.chain_lds(cutcap);
+			hipFuncAttributes fc;
+			bool fits = false;
+			if (!ok || hipFuncGetAttributes(&fc, (const void*) v.chain) != hipSuccess) ok = false;
+			else if ((size_t) fc.sharedSizeBytes + (size_t) lc + 256 <= 160 * 1024) {
+				if (lc <= lim.chain[i]) fits = true;
+				else if (hipFuncSetAttribute((const void*) v.chain, hipFuncAttributeMaxDynamicSharedMemorySize, lc) == hipSuccess) { lim.chain[i] = lc; fits = true; }
+				else (void) hipGetLastError();   // (a build that does not fit is skipped, not an error)
+			}
+			if (!fits) nav->chain_ok[v.zi()] = false;
 		}
-		nav->chain_ok[0] = fits[0] && fits[3] && fits[4] && fits[7];
-		nav->chain_ok[1] = fits[1] && fits[5];
-		nav->chain_ok[2] = fits[2] && fits[6];
+		if (raise_prune) lim.prune = lp;
 		ok = ok && hipFuncSetAttribute((const void*) k_plan_migration, hipFuncAttributeMaxDynamicSharedMemorySize, PLAN_LDS_MAX + 1024) == hipSuccess;
 		hipFuncAttributes fa;
 		if (ok && hipFuncGetAttributes(&fa, (const void*) k_normalise_resample) == hipSuccess) {
@@ -1014,39 +1002,9 @@ void phd_destroy(phd_navigator* nav)
 	if (nav->multi) { multi_destroy(nav); return; }
 	enter(nav);
 	if (nav->stream) hipStreamSynchronize(nav->stream);
-	for (int i = 0; i < 3; i++) {
-		hipFree(nav->bank[i].mix); hipFree(nav->bank[i].count); hipFree(nav->bank[i].poses); hipFree(nav->bank[i].weights);
-	}
-	hipFree(nav->d_sel); hipFree(nav->d_inslot); hipFree(nav->d_mslot); hipFree(nav->d_z); hipFree(nav->d_emit_w); hipFree(nav->d_emit_idx); hipFree(nav->d_emit_rec);
-	hipFree(nav->d_emit_count); hipFree(nav->d_born_count); hipFree(nav->d_born_k); hipFree(nav->d_born_mean);
-	hipFree(nav->d_alpha); hipFree(nav->d_setll); hipFree(nav->d_src);
-	hipFree(nav->d_murty); hipFree(nav->d_bigws); hipFree(nav->d_bigws_used); hipFree(nav->d_jscratch); hipFree(nav->d_dsync); hipFree(nav->d_stamps); hipFree(nav->d_srec); hipFree(nav->d_outw); hipFree(nav->d_wcopy); hipFree(nav->d_cover); hipFree(nav->d_motion); hipFree(nav->d_quasi); hipFree(nav->d_alm); hipFree(nav->d_aJ); hipFree(nav->d_account); hipFree(nav->d_cand_count); hipFree(nav->d_denom); hipFree(nav->d_cand); hipFree(nav->d_gw); hipFree(nav->d_send); hipFree(nav->d_recv); hipFree(nav->d_plan); hipFree(nav->d_nrd); hipFree(nav->d_nri);
-	hipFree(nav->d_lw); hipFree(nav->d_dst_tab); hipFree(nav->d_recv_tab); hipFree(nav->plan.code); hipFree(nav->plan.fslot); hipFree(nav->plan.sendlist); hipFree(nav->plan.senddst); hipFree(nav->plan.counts);
-	if (nav->h_counts) hipHostFree(nav->h_counts);
 	for (void* q : nav->ipc_opened) hipIpcCloseMemHandle(q);
-	hipFree(nav->d_graw);
-	if (nav->h_quasi) hipHostFree(nav->h_quasi);
-	if (nav->h_status) hipHostFree(nav->h_status);
 	for (Timer& t : nav->timers) { hipEventDestroy(t.t0); hipEventDestroy(t.t1); }
-	for (int i = 0; i < 2; i++) {
-		if (nav->h_stage[i]) hipHostFree(nav->h_stage[i]);
-		if (nav->ev_stage[i]) hipEventDestroy(nav->ev_stage[i]);
-	}
-	hipFree(nav->d_stage);
-	for (int i = 0; i < 2; i++) {
-		if (nav->h_depth[i]) hipHostFree(nav->h_depth[i]);
-		if (nav->ev_depth[i]) hipEventDestroy(nav->ev_depth[i]);
-	}
-	hipFree(nav->d_depth);
-	if (nav->own_stream) hipStreamDestroy(nav->own_stream);
-	for (int i = 0; i < phd_navigator::MAXSPLIT - 1; i++) {
-		if (nav->aux[i]) hipStreamDestroy(nav->aux[i]);
-		if (nav->ev_join[i]) hipEventDestroy(nav->ev_join[i]);
-	}
-	if (nav->ev_fork) hipEventDestroy(nav->ev_fork);
-	if (nav->ev_res) hipEventDestroy(nav->ev_res);
-	hipFree(nav->d_biglist); hipFree(nav->d_ratio);
-	delete nav;
+	delete nav;   // (its owners release the buffers, events and streams; the device is current: enter)
 }
 
 const char* phd_last_error(const phd_navigator* nav) { return nav ? nav->err.c_str() : "null handle"; }
@@ -1102,7 +1060,6 @@ int phd_set_poses(phd_navigator* nav, const double* poses7, int nparticles)
 	if (nparticles != nav->P || !poses7) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_poses: particle count mismatch");
 	FINITE_OR_FAIL(nav, poses7, (size_t) nparticles * 7, "phd_set_poses");
 	if (nav->multi) return multi_set_small(nav, poses7, nullptr, nparticles);
-	if (nparticles != nav->P || !poses7) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_poses: particle count mismatch");
 	enter(nav);
 	// the bank that holds the current poses is known to the device (the roles rotate there, at the end of a step): the poses
 	// are staged and stored by a kernel that resolves it, so this is correct right behind phd_step_async and never waits
@@ -1127,7 +1084,6 @@ int phd_update_motion(phd_navigator* nav, const double* odometry6, const double*
 	FINITE_OR_FAIL(nav, noise6, (size_t) nparticles * 6, "phd_update_motion");
 	if (nav->multi) return multi_update_motion(nav, odometry6, noise6, nparticles, perfect_still);
 	if (nav->prm.model != PHD_MODEL_PRM3D) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_update_motion: Pose3D odometry, the PRM3D model only");
-	if (!odometry6 || nparticles != nav->P) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_update_motion: particle count mismatch");
 	enter(nav);
 	bool zero = true;
 	for (int t = 0; t < 6; t++) zero = zero && odometry6[t] == 0;
@@ -1167,8 +1123,8 @@ static int quasi_batch(phd_navigator* nav, const double* poses7, int nposes, con
 	const size_t cap = (size_t) nav->Pcap * 14 + (size_t) nav->Jcap * 3 + 256 * 3 + 2;
 	const size_t op = 0, ol = op + (size_t) nposes * 7, oz = ol + (size_t) nlandmarks * 3, of = oz + (size_t) nmeasurements * 3, ou = of + 1,
 	             oo = ou + 1, og = oo + nposes, end = og + (gradients6 ? (size_t) nposes * 6 : 0);
-	if (!nav->d_quasi) HC(hipMalloc((void**) &nav->d_quasi, cap * 8));
-	if (!nav->h_quasi) HC(hipHostMalloc((void**) &nav->h_quasi, cap * 8, hipHostMallocDefault));
+	if (!nav->d_quasi) HC(nav->d_quasi.alloc(cap));
+	if (!nav->h_quasi) HC(nav->h_quasi.alloc(cap, hipHostMallocDefault));
 	double* const hq = nav->h_quasi;
 	std::memcpy(hq + op, poses7, (size_t) nposes * 7 * 8);
 	if (nlandmarks) std::memcpy(hq + ol, landmarks3, (size_t) nlandmarks * 3 * 8);
@@ -1184,12 +1140,7 @@ static int quasi_batch(phd_navigator* nav, const double* poses7, int nposes, con
 	b.flags = (int*) (nav->d_quasi + of);
 	b.bigws_used = (unsigned long long*) (nav->d_quasi + ou);
 	const bool gradient = gradients6 != nullptr;
-	int rc;
-	switch (zb_of(nmeasurements)) {
-	case 1:  rc = launch_quasi<1>(nav, b, nposes, gradient); break;
-	case 2:  rc = launch_quasi<2>(nav, b, nposes, gradient); break;
-	default: rc = launch_quasi<4>(nav, b, nposes, gradient); break;
-	}
+	const int rc = launch_quasi(nav, b, nposes, gradient);
 	if (rc) return rc;
 	HC(hipMemcpyAsync(hq + of, nav->d_quasi + of, (end - of) * 8, hipMemcpyDeviceToHost, nav->stream));
 	HC(hipStreamSynchronize(nav->stream));
@@ -1228,12 +1179,12 @@ int phd_test_pairing(phd_navigator* nav, const double* matrix, int n, int mode, 
 	}
 	enter(nav);
 	HC(hipStreamSynchronize(nav->stream));
-	double* dm = nullptr; int* da = nullptr; double* dv = nullptr; int* dc = nullptr; char* dbig = nullptr;
-	HC(hipMalloc((void**) &dm, (size_t) n * n * 8));
-	if (n > MURTY_NMAX) HC(hipMalloc((void**) &dbig, murty_big_bytes(n)));
-	HC(hipMalloc((void**) &da, (size_t) maxcount * n * 4));
-	HC(hipMalloc((void**) &dv, (size_t) maxcount * 8));
-	HC(hipMalloc((void**) &dc, 4));
+	DevBuf<double> dm, dv; DevBuf<int> da, dc; DevBuf<char> dbig;
+	HC(dm.alloc((size_t) n * n));
+	if (n > MURTY_NMAX) HC(dbig.alloc(murty_big_bytes(n)));
+	HC(da.alloc((size_t) maxcount * n));
+	HC(dv.alloc(maxcount));
+	HC(dc.alloc(1));
 	hipError_t e = hipMemcpy(dm, matrix, (size_t) n * n * 8, hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
 		hipMemset(da, 0xff, (size_t) maxcount * n * 4);
@@ -1245,7 +1196,6 @@ int phd_test_pairing(phd_navigator* nav, const double* matrix, int n, int mode, 
 	const int k = std::min(m, maxcount);
 	if (e == hipSuccess && k > 0) e = hipMemcpy(assignments, da, (size_t) k * n * 4, hipMemcpyDeviceToHost);
 	if (e == hipSuccess && k > 0) e = hipMemcpy(values, dv, (size_t) k * 8, hipMemcpyDeviceToHost);
-	hipFree(dm); hipFree(da); hipFree(dv); hipFree(dc); hipFree(dbig);
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_pairing: ") + hipGetErrorString(e));
 	*count = m;
 	return PHD_OK;
@@ -1257,7 +1207,6 @@ int phd_set_weights(phd_navigator* nav, const double* weights, int nparticles)
 	if (nparticles != nav->P || !weights) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_weights: particle count mismatch");
 	FINITE_OR_FAIL(nav, weights, nparticles, "phd_set_weights");
 	if (nav->multi) return multi_set_small(nav, nullptr, weights, nparticles);
-	if (nparticles != nav->P || !weights) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_weights: particle count mismatch");
 	enter(nav);
 	double* hs = stage_acquire(nav);
 	std::memcpy(hs, weights, (size_t) nparticles * 8);
@@ -1389,9 +1338,6 @@ int phd_set_measurements(phd_navigator* nav, const double* z3, int nmeasurements
 	if (nmeasurements < 0 || nmeasurements > nav->prm.max_measurements || (nmeasurements > 0 && !z3)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_measurements: count out of range");
 	FINITE_OR_FAIL(nav, z3, (size_t) nmeasurements * 3, "phd_set_measurements");
 	if (nav->multi) return multi_set_measurements(nav, z3, nmeasurements);
-	if (nmeasurements < 0 || nmeasurements > nav->prm.max_measurements || (nmeasurements > 0 && !z3)) {
-		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_set_measurements: count out of range");
-	}
 	enter(nav);
 	if (nmeasurements > 0) {
 		double* hs = stage_acquire(nav);
@@ -1426,19 +1372,13 @@ int phd_set_depth_map(phd_navigator* nav, const float* depth, int width, int hei
 	if (n > nav->depthcap || n > nav->hdepthcap) {
 		HC(hipStreamSynchronize(nav->stream));
 		for (int s = 0; s < phd_navigator::MAXSPLIT - 1; s++) if (nav->aux[s]) HC(hipStreamSynchronize(nav->aux[s]));
-		float* nd = nullptr; float* nh[2] = {nullptr, nullptr};
-		hipError_t e = hipMalloc((void**) &nd, n * 4);
-		for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**) &nh[i], n * 4, hipHostMallocDefault);
-		for (int i = 0; i < 2 && e == hipSuccess; i++) if (!nav->ev_depth[i]) e = hipEventCreateWithFlags(&nav->ev_depth[i], hipEventDisableTiming);
-		if (e != hipSuccess) {
-			hipFree(nd);
-			for (int i = 0; i < 2; i++) if (nh[i]) hipHostFree(nh[i]);
-			return nav->fail(PHD_ERR_DEVICE, std::string("phd_set_depth_map: allocation: ") + hipGetErrorString(e));
-		}
-		hipFree(nav->d_depth);
-		for (int i = 0; i < 2; i++) if (nav->h_depth[i]) hipHostFree(nav->h_depth[i]);
-		nav->d_depth = nd; nav->depthcap = n;
-		nav->h_depth[0] = nh[0]; nav->h_depth[1] = nh[1]; nav->hdepthcap = n;
+		DevBuf<float> nd; PinBuf<float> nh[2];
+		hipError_t e = nd.alloc(n);
+		for (int i = 0; i < 2 && e == hipSuccess; i++) e = nh[i].alloc(n, hipHostMallocDefault);
+		for (int i = 0; i < 2 && e == hipSuccess; i++) if (!nav->ev_depth[i]) e = hipEventCreateWithFlags(nav->ev_depth[i].put(), hipEventDisableTiming);
+		if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_set_depth_map: allocation: ") + hipGetErrorString(e));
+		nav->d_depth = std::move(nd); nav->depthcap = n;   // (the old buffers go here, behind the new ones)
+		nav->h_depth[0] = std::move(nh[0]); nav->h_depth[1] = std::move(nh[1]); nav->hdepthcap = n;
 		nav->depth_used[0] = nav->depth_used[1] = false;
 	}
 	nav->depth_i ^= 1;
@@ -1460,17 +1400,16 @@ int phd_test_detection_probability(phd_navigator* nav, const double* z3, int n, 
 	if (n < 0 || (n > 0 && (!z3 || !out))) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_test_detection_probability: n >= 0 points and both buffers");
 	if (n == 0) return PHD_OK;
 	enter(nav);
-	double* dz = nullptr; double* dout = nullptr;
-	HC(hipMalloc((void**) &dz, (size_t) n * 3 * 8));
-	hipError_t e = hipMalloc((void**) &dout, (size_t) n * 8);
+	DevBuf<double> dz, dout;
+	HC(dz.alloc((size_t) n * 3));
+	hipError_t e = dout.alloc(n);
 	if (e == hipSuccess) e = hipMemcpyAsync(dz, z3, (size_t) n * 3 * 8, hipMemcpyHostToDevice, nav->stream);
 	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_test_detection_probability, dim3((n + 255) / 256), dim3(256), 0, nav->stream, nav->dp, (const double*) dz, n, dout);
+		hipLaunchKernelGGL(k_test_detection_probability, dim3((n + 255) / 256), dim3(256), 0, nav->stream, nav->dp, (const double*) dz, n, (double*) dout);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t) n * 8, hipMemcpyDeviceToHost, nav->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(nav->stream);
-	hipFree(dz); hipFree(dout);
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_detection_probability: ") + hipGetErrorString(e));
 	return PHD_OK;
 }
@@ -1489,11 +1428,10 @@ int phd_set_association_workspace(phd_navigator* nav, int64_t bytes)
 	if (nav->multi) return multi_forward_int(nav, 1, bytes);
 	enter(nav);
 	HC(hipStreamSynchronize(nav->stream));
-	hipFree(nav->d_bigws);
-	nav->d_bigws = nullptr;
+	nav->d_bigws.reset();
 	nav->bigws_bytes = 0;
 	if (bytes > 0) {
-		HC(hipMalloc((void**) &nav->d_bigws, (size_t) bytes));
+		HC(nav->d_bigws.alloc((size_t) bytes));
 		nav->bigws_bytes = (unsigned long long) bytes;
 	}
 	HC(hipMemset(nav->d_bigws_used, 0, 8));
@@ -1516,14 +1454,13 @@ int phd_set_all_pairs(phd_navigator* nav, uint8_t all_pairs)
 	return PHD_OK;
 }
 
-// Does a step of this handle run as the one-launch chain (launch_map_kernels), and may that launch end the step itself?
+// Does a step of this handle run as the one-launch chain (launch_map), and may that launch end the step itself?
 static bool chain_folds_normalise(const phd_navigator* nav)
 {
-	const int zb = zb_of(nav->M), zi = zb == 1 ? 0 : (zb == 2 ? 1 : 2);
-	if (!nav->fold_nr || !nav->chain_ok[zi] || nav->P > nav->chain_max) return false;
+	const StepVariant& v = variant(nav->M, nav->dp.depth != nullptr);
+	if (!nav->fold_nr || !nav->chain_ok[v.zi()] || nav->P > nav->chain_max) return false;
 	const size_t lw = (size_t) ((nav->P + 255) / 256) * 257 * 8;   // the weight vector, chunk-transposed, in the chain's pool
-	const size_t pool = zb == 1 ? chain_lds_bytes<1>(nav->cutcap) : (zb == 2 ? chain_lds_bytes<2>(nav->cutcap) : chain_lds_bytes<4>(nav->cutcap));
-	return lw <= pool;
+	return lw <= (size_t) v.chain_lds(nav->cutcap);
 }
 
 int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
@@ -1547,8 +1484,7 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 	// chain starts second finishes last (`lagger`), k_normalise_resample goes behind ITS k_alpha_density (the other stream's
 	// event is long recorded), its next k_sweep behind that — and so it leads the next step, the other stream, which waits for
 	// the event, lags and takes the end of that one.
-	const int zi_ = zb_of(nav->M) == 1 ? 0 : (zb_of(nav->M) == 2 ? 1 : 2);
-	const bool chain = nav->chain_ok[zi_] && nav->P <= nav->chain_max;
+	const bool chain = nav->chain_ok[variant(nav->M, nav->dp.depth != nullptr).zi()] && nav->P <= nav->chain_max;
 	const int want = nav->nsplit > 0 ? nav->nsplit : (nav->P >= 1024 ? 2 : 1);
 	const bool pipe = nav->pipeline && !chain && want == 2 && nav->P >= 2 && nav->stream == nav->own_stream;
 	int rc;
@@ -1578,10 +1514,11 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 			HC(hipEventRecord(nav->ev_join[0], X));
 			HC(hipStreamWaitEvent(L, nav->ev_join[0], 0));
 		}
-		timer_begin(nav, T_NR, L);
-		rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
-		                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE, L);
-		timer_end(nav, T_NR, L);
+		{
+			Timed t(nav, T_NR, L);
+			rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
+			                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE, L);
+		}
 		if (rc) { nav->pipe_ok = false; return rc; }
 		if (dev) {
 			hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, X, b.ticket + 1, nav->step_seq, nav->d_flags);
@@ -1600,11 +1537,12 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 		if (rc) return rc;
 		if (!folded) {
 			b.defer = nav->last_defer;
-			timer_begin(nav, T_NR);
-			// the same launch hands the resampled particles their small arrays and rotates the bank roles (rotate_roles)
-			rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
-			                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE);
-			timer_end(nav, T_NR);
+			{
+				Timed t(nav, T_NR, nav->stream);
+				// the same launch hands the resampled particles their small arrays and rotates the bank roles (rotate_roles)
+				rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
+				                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE);
+			}
 			if (rc) return rc;
 		}
 	}
@@ -1819,17 +1757,15 @@ static int ensure_gw(phd_navigator* nav, int n, bool shared = false)
 	if (n <= nav->gwcap) return PHD_OK;
 	if (nav->gw_shared) return nav->fail(PHD_ERR_GENERIC, "the gathered-weight vector of a shard cannot grow (other shards hold its address)");
 	HC(hipStreamSynchronize(nav->stream));
-	hipFree(nav->d_gw);
-	nav->d_gw = nullptr;
-	hipFree(nav->d_plan);
-	nav->d_plan = nullptr;
+	nav->d_gw.reset();
+	nav->d_plan.reset();
 	// (a multi-device handle's shards store their weights into each other's vectors: fine-grained, as the receive buffers)
-	if (!shared || getenv("PHD_COARSE_RECV") || hipExtMallocWithFlags((void**) &nav->d_gw, ((size_t) n + PHD_MAX_DEVICES) * 8, hipDeviceMallocFinegrained) != hipSuccess) {
+	if (!shared || getenv("PHD_COARSE_RECV") || hipExtMallocWithFlags((void**) nav->d_gw.put(), ((size_t) n + PHD_MAX_DEVICES) * 8, hipDeviceMallocFinegrained) != hipSuccess) {
 		(void) hipGetLastError();
-		nav->d_gw = nullptr;
-		HC(hipMalloc((void**) &nav->d_gw, ((size_t) n + PHD_MAX_DEVICES) * 8));
+		(void) nav->d_gw.release();   // (whatever the failed call left in it is nothing to free)
+		HC(nav->d_gw.alloc((size_t) n + PHD_MAX_DEVICES));
 	}
-	HC(hipMalloc((void**) &nav->d_plan, (size_t) n * 4));
+	HC(nav->d_plan.alloc(n));
 	nav->gwcap = n;
 	return PHD_OK;
 }
@@ -1843,10 +1779,10 @@ int phd_resample(phd_navigator* nav, const double* weights, int nparticles, doub
 	enter(nav);
 	HC(hipStreamSynchronize(nav->stream));
 	// (buffers of its own: the gathered-weight vector of a sharded handle is known to other shards by address)
-	double* d_w = nullptr;
-	int* d_src2 = nullptr;
-	HC(hipMalloc((void**) &d_w, (size_t) nparticles * 8));
-	if (hipMalloc((void**) &d_src2, (size_t) nparticles * 4 + 8) != hipSuccess) { hipFree(d_w); return nav->fail(PHD_ERR_DEVICE, "phd_resample: out of device memory"); }
+	DevBuf<double> d_w;
+	DevBuf<int> d_src2;
+	HC(d_w.alloc(nparticles));
+	if (d_src2.alloc((size_t) nparticles + 2) != hipSuccess) return nav->fail(PHD_ERR_DEVICE, "phd_resample: out of device memory");
 	hipError_t e = hipMemcpy(d_w, weights, (size_t) nparticles * 8, hipMemcpyHostToDevice);
 	StepBufs b = make_bufs(nav);
 	int rc = (e == hipSuccess) ? launch_normalise(nav, b, d_w, nparticles, u_resample, 1, 1, d_src2 + 2, d_src2) : PHD_OK;
@@ -1854,7 +1790,6 @@ int phd_resample(phd_navigator* nav, const double* weights, int nparticles, doub
 	int info[2] = {0, 0};
 	if (e == hipSuccess) e = hipMemcpy(sources, d_src2 + 2, (size_t) nparticles * 4, hipMemcpyDeviceToHost);
 	if (e == hipSuccess) e = hipMemcpy(info, d_src2, 8, hipMemcpyDeviceToHost);
-	hipFree(d_src2); hipFree(d_w);
 	if (rc) return rc;
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, hipGetErrorString(e));
 	if (best_particle) *best_particle = info[0];
@@ -1868,17 +1803,16 @@ int phd_particle_depleted(phd_navigator* nav, const double* weights, int npartic
 	if (nparticles < 1 || !weights || !depleted) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_particle_depleted: bad arguments");
 	enter(nav);
 	HC(hipStreamSynchronize(nav->stream));
-	double* d_w = nullptr;
-	int* d_tmp = nullptr;
-	HC(hipMalloc((void**) &d_w, (size_t) nparticles * 8));
-	if (hipMalloc((void**) &d_tmp, (size_t) nparticles * 4 + 8) != hipSuccess) { hipFree(d_w); return nav->fail(PHD_ERR_DEVICE, "phd_particle_depleted: out of device memory"); }
+	DevBuf<double> d_w;
+	DevBuf<int> d_tmp;
+	HC(d_w.alloc(nparticles));
+	if (d_tmp.alloc((size_t) nparticles + 2) != hipSuccess) return nav->fail(PHD_ERR_DEVICE, "phd_particle_depleted: out of device memory");
 	hipError_t e = hipMemcpy(d_w, weights, (size_t) nparticles * 8, hipMemcpyHostToDevice);
 	StepBufs b = make_bufs(nav);
 	int rc = (e == hipSuccess) ? launch_normalise(nav, b, d_w, nparticles, 0.5, 0, 1, d_tmp + 2, d_tmp) : PHD_OK;
 	if (e == hipSuccess) e = hipStreamSynchronize(nav->stream);
 	int info[2] = {0, 0};
 	if (e == hipSuccess) e = hipMemcpy(info, d_tmp, 8, hipMemcpyDeviceToHost);
-	hipFree(d_tmp); hipFree(d_w);
 	if (rc) return rc;
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, hipGetErrorString(e));
 	*depleted = info[1] ? 1 : 0;
@@ -1965,17 +1899,16 @@ int phd_last_timing_counts(phd_navigator* nav, const int** counts)
 // most one rank).
 static void free_sharded(phd_navigator* nav)
 {
-	hipFree(nav->d_lw); nav->d_lw = nullptr;
-	hipFree(nav->d_dst_tab); nav->d_dst_tab = nullptr;
-	hipFree(nav->plan.code); hipFree(nav->plan.fslot); hipFree(nav->plan.sendlist); hipFree(nav->plan.senddst); hipFree(nav->plan.counts);
+	nav->d_lw.reset();
+	nav->d_dst_tab.reset();
+	nav->plan_code.reset(); nav->plan_fslot.reset(); nav->plan_sendlist.reset(); nav->plan_senddst.reset(); nav->plan_counts.reset();
 	nav->plan = MigPlan{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-	if (nav->h_counts) hipHostFree(nav->h_counts);
-	nav->h_counts = nullptr;
-	hipFree(nav->d_mslot); nav->d_mslot = nullptr;
-	hipFree(nav->d_plang); nav->d_plang = nullptr;
-	hipFree(nav->d_send); nav->d_send = nullptr;
-	hipFree(nav->d_recv); nav->d_recv = nullptr;
-	hipFree(nav->d_recv_tab); nav->d_recv_tab = nullptr;
+	nav->h_counts.reset();
+	nav->d_mslot.reset();
+	nav->d_plang.reset();
+	nav->d_send.reset();
+	nav->d_recv.reset();
+	nav->d_recv_tab.reset();
 	nav->sharded_ready = false;
 }
 
@@ -1985,7 +1918,7 @@ static int ensure_sharded(phd_navigator* nav, bool need_send = true)
 		if (need_send && !nav->d_send) {   // (a handle first used without a send buffer: push-only hosts never need one)
 			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
 			enter(nav);
-			HC(hipMalloc((void**) &nav->d_send, (size_t) nav->sendrecs * rec * 8));
+			HC(nav->d_send.alloc((size_t) nav->sendrecs * rec));
 		}
 		return PHD_OK;
 	}
@@ -1998,28 +1931,30 @@ static int ensure_sharded(phd_navigator* nav, bool need_send = true)
 	// half-made set — the flag below is what every user of these buffers asks)
 	hipError_t e = hipSuccess;
 	auto want = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
-	want(hipMalloc((void**) &nav->d_lw, (size_t) (nav->Pcap + 1) * 8));
-	want(hipMalloc((void**) &nav->d_dst_tab, PHD_MAX_DEVICES * sizeof(double*)));
-	if (e == hipSuccess) want(hipMemcpy(nav->d_dst_tab, &nav->d_lw, sizeof(double*), hipMemcpyHostToDevice));
-	want(hipMalloc((void**) &nav->d_recv_tab, PHD_MAX_DEVICES * sizeof(double*)));
-	want(hipMalloc((void**) &nav->plan.code, (size_t) nav->Pcap * 4));
-	want(hipMalloc((void**) &nav->plan.fslot, (size_t) nav->Pcap * 4));
-	want(hipMalloc((void**) &nav->plan.sendlist, (size_t) nav->plan.sendcap * 4));
-	want(hipMalloc((void**) &nav->plan.senddst, (size_t) nav->plan.sendcap * 8));
-	want(hipMalloc((void**) &nav->plan.counts, (2 * PHD_MAX_DEVICES + 8) * 4));
+	want(nav->d_lw.alloc((size_t) nav->Pcap + 1));
+	want(nav->d_dst_tab.alloc(PHD_MAX_DEVICES));
+	double* const lw = nav->d_lw;   // (the table's first entry is the ADDRESS the export buffer has on the device)
+	if (e == hipSuccess) want(hipMemcpy(nav->d_dst_tab, &lw, sizeof(double*), hipMemcpyHostToDevice));
+	want(nav->d_recv_tab.alloc(PHD_MAX_DEVICES));
+	want(nav->plan_code.alloc(nav->Pcap));
+	want(nav->plan_fslot.alloc(nav->Pcap));
+	want(nav->plan_sendlist.alloc(nav->plan.sendcap));
+	want(nav->plan_senddst.alloc(nav->plan.sendcap));
+	want(nav->plan_counts.alloc(2 * PHD_MAX_DEVICES + 8));
+	nav->plan = MigPlan{nav->plan_code, nav->plan_fslot, nav->plan_sendlist, nav->plan_senddst, nav->plan_counts, nav->plan.sendcap};
 	if (e == hipSuccess) want(hipMemset(nav->plan.counts, 0, (2 * PHD_MAX_DEVICES + 8) * 4));
 	// (coherent: the plan kernel's system-scope stores must reach the polling host while the kernel runs, whatever the
 	// runtime's default for mapped host memory is)
-	want(hipHostMalloc((void**) &nav->h_counts, (2 * PHD_MAX_DEVICES + 8) * 4, hipHostMallocMapped | hipHostMallocCoherent));
+	want(nav->h_counts.alloc(2 * PHD_MAX_DEVICES + 8, hipHostMallocMapped | hipHostMallocCoherent));
 	if (e == hipSuccess) std::memset(nav->h_counts, 0, (2 * PHD_MAX_DEVICES + 8) * 4);
-	want(hipMalloc((void**) &nav->d_mslot, (size_t) nav->Pcap * 4));
+	want(nav->d_mslot.alloc(nav->Pcap));
 	{   // k_plan_count / k_plan_lists: [2 sets][cnt 64 x 64 | used Pcap / 32 + 1 | bad 1] | wcg [1024] | lcg [Pcap / 64 + 1]
 		const size_t set = (size_t) PHD_MAX_DEVICES * PHD_MAX_DEVICES + (size_t) (nav->Pcap + 31) / 32 + 2;
 		const size_t words = 2 * set + 1024 + (size_t) nav->Pcap / 64 + 2;
-		want(hipMalloc((void**) &nav->d_plang, words * 4));
+		want(nav->d_plang.alloc(words));
 		if (e == hipSuccess) want(hipMemset(nav->d_plang, 0, words * 4));
 	}
-	if (need_send) want(hipMalloc((void**) &nav->d_send, (size_t) nav->sendrecs * rec * 8));   // (a shard of a multi-device handle packs straight into its peers' receive buffers)
+	if (need_send) want(nav->d_send.alloc((size_t) nav->sendrecs * rec));   // (a shard of a multi-device handle packs straight into its peers' receive buffers)
 	// The receive buffer is written by OTHER devices (peer stores of a multi-device handle's shards, or of other ranks'
 	// processes through IPC) and read here: fine-grained device memory, coherent between agents without cache maintenance —
 	// what RCCL allocates for its own peer-to-peer buffers. (See the head of phd_multi.inc for the visibility argument.)
@@ -2027,11 +1962,11 @@ static int ensure_sharded(phd_navigator* nav, bool need_send = true)
 		// (+ PHD_MAX_DEVICES words behind the records: the landing flags, one per sending rank — k_post_landing)
 		const size_t recv_bytes = ((size_t) nav->recvrecs * rec + PHD_MAX_DEVICES) * 8;
 		nav->recv_finegrained = getenv("PHD_COARSE_RECV") == nullptr &&
-		                        hipExtMallocWithFlags((void**) &nav->d_recv, recv_bytes, hipDeviceMallocFinegrained) == hipSuccess;
+		                        hipExtMallocWithFlags((void**) nav->d_recv.put(), recv_bytes, hipDeviceMallocFinegrained) == hipSuccess;
 		if (!nav->recv_finegrained) {
 			(void) hipGetLastError();
-			nav->d_recv = nullptr;
-			want(hipMalloc((void**) &nav->d_recv, recv_bytes));
+			(void) nav->d_recv.release();   // (whatever the failed call left in it is nothing to free)
+			want(nav->d_recv.alloc(recv_bytes / 8));
 		}
 		if (e == hipSuccess) want(hipMemset(nav->d_recv + (size_t) nav->recvrecs * rec, 0, PHD_MAX_DEVICES * 8));
 	}
@@ -2058,11 +1993,9 @@ static int step_local(phd_navigator* nav, uint8_t onlymapping)
 	rc = launch_map(nav, b, !onlymapping);
 	if (rc) return rc;
 	b.defer = nav->last_defer;
-	timer_begin(nav, T_PW);
 	// (per-rank host: the export buffer holds P + 1 doubles, the step's status word behind the weights)
-	hipLaunchKernelGGL(k_push_weights, dim3((nav->P + 255) / 256), dim3(256), 0, nav->stream, b, (double* const*) nav->d_dst_tab, nav->ndst,
-	                   nav->push_first, nav->gw_shared ? nav->push_flagslot : nav->P);
-	timer_end(nav, T_PW);
+	launch_timed(nav, T_PW, nav->stream, false, k_push_weights, dim3((nav->P + 255) / 256), dim3(256), 0, b, (double* const*) nav->d_dst_tab, nav->ndst,
+	             nav->push_first, nav->gw_shared ? nav->push_flagslot : nav->P);
 	HC(hipGetLastError());
 	return PHD_OK;
 }
@@ -2155,10 +2088,11 @@ static int step_global(phd_navigator* nav, int rank, int world_size, double u, u
 	std::memset(&pg, 0, sizeof pg);
 	if (pgrid) pg = plan_grid_next(nav);
 	bool counted = false;
-	timer_begin(nav, T_NR);
-	rc = launch_normalise(nav, b, nav->d_gw, Pg, u, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_plan, nav->d_info, nullptr, nullptr,
-	                      from_graw ? (const double*) nav->d_graw : nullptr, nav->P, world_size, pgrid ? &pg : nullptr, rank, nav->d_gflags, &counted);
-	timer_end(nav, T_NR);
+	{
+		Timed t(nav, T_NR, nav->stream);
+		rc = launch_normalise(nav, b, nav->d_gw, Pg, u, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_plan, nav->d_info, nullptr, nullptr,
+		                      from_graw ? (const double*) nav->d_graw : nullptr, nav->P, world_size, pgrid ? &pg : nullptr, rank, nav->d_gflags, &counted);
+	}
 	if (rc) return rc;
 	int* hc = nullptr;
 	if (hostcounts) {
@@ -2166,11 +2100,9 @@ static int step_global(phd_navigator* nav, int rank, int world_size, double u, u
 		nav->plan_seq++;
 		nav->plan_waiting = true;
 	}
-	timer_begin(nav, T_PL);
-	rc = launch_plan(nav, b, (const int*) nav->d_plan, (const int*) nav->d_info, (const int*) nav->d_flags, nav->d_gflags, nav->P, world_size, rank, hc,
-	                 nav->plan_seq, (const double*) nav->d_gw, pgrid ? &pg : nullptr, counted);
-	timer_end(nav, T_PL);
-	return rc;
+	Timed t(nav, T_PL, nav->stream);
+	return launch_plan(nav, b, (const int*) nav->d_plan, (const int*) nav->d_info, (const int*) nav->d_flags, nav->d_gflags, nav->P, world_size, rank, hc,
+	                   nav->plan_seq, (const double*) nav->d_gw, pgrid ? &pg : nullptr, counted);
 }
 
 int phd_step_global_async(phd_navigator* nav, int rank, int world_size, double u_resample)
@@ -2199,9 +2131,9 @@ void* phd_device_gather_buffer(phd_navigator* nav, int world_size)
 	const int need = world_size * (nav->Pcap + 1);
 	if (need > nav->grawcap) {
 		if (hipStreamSynchronize(nav->stream) != hipSuccess) return nullptr;
-		hipFree(nav->d_graw);
-		nav->d_graw = nullptr; nav->grawcap = 0;
-		if (hipMalloc((void**) &nav->d_graw, (size_t) need * 8) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
+		nav->d_graw.reset();
+		nav->grawcap = 0;
+		if (nav->d_graw.alloc(need) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
 		hipMemset(nav->d_graw, 0, (size_t) need * 8);
 		nav->grawcap = need;
 	}
@@ -2337,15 +2269,16 @@ int phd_migration_push_async(phd_navigator* nav)
 	enter(nav);
 	if (nav->world <= 1) return PHD_OK;   // (one rank: nothing ever leaves it)
 	StepBufs b = make_bufs(nav);
-	timer_begin(nav, T_PK);
-	hipLaunchKernelGGL(k_pack_particles, dim3(std::min(nav->plan.sendcap, 256)), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (double*) nullptr,
-	                   (double* const*) nav->d_recv_tab);
-	if (nav->landing_flags && nav->world > 1) {
-		const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
-		hipLaunchKernelGGL(k_post_landing, dim3(1), dim3(64), 0, nav->stream, (double* const*) nav->d_recv_tab, nav->world, nav->rank,
-		                   (size_t) nav->recvrecs * rec, nav->landing_seq);
+	{
+		Timed t(nav, T_PK, nav->stream);
+		hipLaunchKernelGGL(k_pack_particles, dim3(std::min(nav->plan.sendcap, 256)), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (double*) nullptr,
+		                   (double* const*) nav->d_recv_tab);
+		if (nav->landing_flags && nav->world > 1) {
+			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
+			hipLaunchKernelGGL(k_post_landing, dim3(1), dim3(64), 0, nav->stream, (double* const*) nav->d_recv_tab, nav->world, nav->rank,
+			                   (size_t) nav->recvrecs * rec, nav->landing_seq);
+		}
 	}
-	timer_end(nav, T_PK);
 	HC(hipGetLastError());
 	return PHD_OK;
 }
@@ -2423,8 +2356,8 @@ int phd_test_migration_plan(phd_navigator* nav, const int32_t* gsrc, int particl
 	int rc = ensure_sharded(nav);
 	if (rc) return rc;
 	HC(hipStreamSynchronize(nav->stream));
-	int* d_g = nullptr;
-	HC(hipMalloc((void**) &d_g, ((size_t) Pl * n + 4) * 4));
+	DevBuf<int> d_g;
+	HC(d_g.alloc((size_t) Pl * n + 4));
 	int* d_i = d_g + (size_t) Pl * n;   // info[2], a clear status word
 	const int info[3] = {0, resampled ? 1 : 0, 0};
 	hipError_t e = hipMemcpy(d_g, gsrc, (size_t) Pl * n * 4, hipMemcpyHostToDevice);
@@ -2432,12 +2365,11 @@ int phd_test_migration_plan(phd_navigator* nav, const int32_t* gsrc, int particl
 	if (e == hipSuccess) {
 		rc = launch_plan(nav, make_bufs(nav), (const int*) d_g, (const int*) d_i, (const int*) (d_i + 2), (const double*) nullptr, Pl, n, rank, (int*) nullptr, 0,
 		                 (const double*) nullptr);
-		if (rc) { hipFree(d_g); return rc; }
+		if (rc) return rc;
 		e = hipStreamSynchronize(nav->stream);
 	}
 	std::vector<int> c(2 * n + 4);
 	if (e == hipSuccess) e = hipMemcpy(c.data(), nav->plan.counts, c.size() * 4, hipMemcpyDeviceToHost);
-	hipFree(d_g);
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_migration_plan: ") + hipGetErrorString(e));
 	for (int r = 0; r < n; r++) { send_counts[r] = c[r]; recv_counts[r] = c[n + r]; }
 	*nsend = c[2 * n]; *nrecv = c[2 * n + 1]; *status = c[2 * n + 2];
@@ -2522,10 +2454,8 @@ int phd_migration_pack_async(phd_navigator* nav)
 	if (!nav->sharded_ready || nav->plan_on_device) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_migration_pack_async: no plan known to the host (phd_step_global_async, phd_migration_plan first)");
 	if (nav->nsend == 0) return PHD_OK;   // (the per-rank host knows the counts)
 	StepBufs b = make_bufs(nav);
-	timer_begin(nav, T_PK);
-	hipLaunchKernelGGL(k_pack_particles, dim3(std::min(nav->nsend, pack_grid(nav))), dim3(256), 0, nav->stream, b, nav->plan, nav->world, nav->d_send,
-	                   (double* const*) nullptr);
-	timer_end(nav, T_PK);
+	launch_timed(nav, T_PK, nav->stream, false, k_pack_particles, dim3(std::min(nav->nsend, pack_grid(nav))), dim3(256), 0, b, nav->plan, nav->world,
+	             (double*) nav->d_send, (double* const*) nullptr);
 	HC(hipGetLastError());
 	return PHD_OK;
 }
@@ -2537,19 +2467,20 @@ static int step_finish(phd_navigator* nav)
 	StepBufs b = make_bufs(nav);
 	int* sel_next = nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE;
 	nav->d_res_slots = nav->d_mslot;
-	timer_begin(nav, T_GR);
-	const unsigned long long* landing = nullptr;
-	if (nav->landing_flags && nav->plan_on_device && nav->world > 1) {
-		const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
-		landing = (const unsigned long long*) (nav->d_recv + (size_t) nav->recvrecs * rec);
-		if (!nav->landing_inline) {   // one wave waits, in front of the launch that reads (k_wait_landing)
-			hipLaunchKernelGGL(k_wait_landing, dim3(1), dim3(64), 0, nav->stream, nav->plan, nav->world, landing, nav->landing_seq, nav->landing_ticks, nav->d_flags);
-			landing = nullptr;
+	{
+		Timed t(nav, T_GR, nav->stream);
+		const unsigned long long* landing = nullptr;
+		if (nav->landing_flags && nav->plan_on_device && nav->world > 1) {
+			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
+			landing = (const unsigned long long*) (nav->d_recv + (size_t) nav->recvrecs * rec);
+			if (!nav->landing_inline) {   // one wave waits, in front of the launch that reads (k_wait_landing)
+				hipLaunchKernelGGL(k_wait_landing, dim3(1), dim3(64), 0, nav->stream, nav->plan, nav->world, landing, nav->landing_seq, nav->landing_ticks, nav->d_flags);
+				landing = nullptr;
+			}
 		}
+		hipLaunchKernelGGL(k_finish_sharded, dim3(nav->P), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (const double*) nav->d_recv,
+		                   1.0 / (double) nav->last_world_particles, sel_next, nav->frozen ? 1 : 0, nav->d_inslot, nav->d_mslot, landing, nav->landing_seq, nav->landing_ticks);
 	}
-	hipLaunchKernelGGL(k_finish_sharded, dim3(nav->P), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (const double*) nav->d_recv,
-	                   1.0 / (double) nav->last_world_particles, sel_next, nav->frozen ? 1 : 0, nav->d_inslot, nav->d_mslot, landing, nav->landing_seq, nav->landing_ticks);
-	timer_end(nav, T_GR);
 	HC(hipGetLastError());
 	nav->parity ^= 1;
 	nav->stage_valid = false;

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 THREADS = min(16, os.cpu_count() or 1)   # (a command on the GPU machines gets 16 CPUs; os.cpu_count() shows the whole box)
 
-KERNELS = {   # what launch_map_kernels launches per sub-range, by path
+KERNELS = {   # what launch_map launches per sub-range, by path
     "chain": {"k_particle_chain"},
     "separate-fused": {"k_sweep", "k_emit_prune", "k_alpha_assoc", "k_alpha_density"},
     "separate-unfused": {"k_sweep", "k_emit_finish", "k_prune_merge", "k_alpha_assoc", "k_alpha_density"},
@@ -40,7 +40,7 @@ def zb_of(M):
 
 
 def klass(M):
-    """the measurement-block class of launch_map_kernels: HALF (one block, two components per visit), ZB1, ZB2, ZB4"""
+    """the measurement-block class of launch_map: HALF (one block, two components per visit), ZB1, ZB2, ZB4"""
     return "half" if M <= 32 else "zb%d" % zb_of(M)
 
 
