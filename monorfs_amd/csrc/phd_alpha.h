@@ -677,9 +677,6 @@ __global__ __launch_bounds__(64) void k_test_pairing(MurtyNodes* nodes, char* bi
 // Arrays indexed by landmark live in LDS while the map estimate has at most ALPHA_JL landmarks; a larger
 // estimate (up to Jcap) moves them to a per-particle slab in HBM, reached through the same (flat) pointers.
 #define ALPHA_JL 256
-#ifndef ALPHA_DEFER_ROWS
-#define ALPHA_DEFER_ROWS 10   // a particle with an association cluster of more rows than this is left to the big-cluster workers (DEFER, below)
-#endif
 
 struct AlphaLds {
 	int zs, red, lm, pick, scr;                 // persistent, offsets in doubles
@@ -750,12 +747,6 @@ __host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap)
 #define QGRAD_G2_CLUSTERS 64                                  // headers / weights of the first pass kept in LDS for the ordered replay
 #define QGRAD_G2_WEIGHTS 384
 #define QGRAD_HDR 10                                         // doubles per cluster in the particle's scratch: pairings, G[6], list offset, finite
-// DEFER (the step's k_alpha_assoc; 0: everything here): the ordered replay of the clusters of more than 5 rows — best-first
-//                enumeration by ONE wave, up to 200 assignment problems per cluster — is rare per particle and enormous when
-//                it happens (config S: 5 % of the particles, 15 times the median workgroup's lifetime: the launch waited for
-//                them). 1: a particle that needs it is put on the launch's list (StepBufs::biglist) and gets no set
-//                log-likelihood here; 2: k_alpha_big, one workgroup per listed particle (pin >= 0), runs the body again WITH the
-//                replay — on a stream of its own, beside k_alpha_density, which does not need the value (k_alpha_combine does).
 #ifndef DENS_JL
 #define DENS_JL 128   // landmarks whose partial sums stay in LDS
 #endif
@@ -764,8 +755,8 @@ __host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap)
 // which then run BESIDE the association below instead of behind it; *helper_go says whether it did.
 __device__ __forceinline__ unsigned int my_xcd() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u; }   // HW_REG_XCC_ID
 
-template <int ZB, bool QUASI, bool GRAD = false, int TAG = 0, int DEFER = 0, bool DEPTH = false>
-__device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const StepBufs& a, int ncap, double* smem, double* gws = nullptr, int pin = -1,
+template <int ZB, bool QUASI, bool GRAD = false, int TAG = 0, bool DEPTH = false>
+__device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const StepBufs& a, int ncap, double* smem, double* gws = nullptr,
                                                  int* helper_go = nullptr)
 {
 	constexpr int MP = ZB * 64;
@@ -775,18 +766,17 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 	double* zs   = smem + lay.zs;          // [MP][3] measurements
 	double* red  = smem + lay.red;         // [256] reduction scratch
 	double* etab = red;                    // [256] exp table (filled before the cluster sums, once `red` is idle)
-	__shared__ int s_J, s_changed, s_nroots, s_big, s_huge;
+	__shared__ int s_J, s_changed, s_nroots, s_big;
 	__shared__ double s_ccount, s_total;
 	__shared__ int s_ebump, s_g2lds;                                                    // gradient mode (see the first pass below)
 	__shared__ double s_g2[GRAD ? QGRAD_G2_CLUSTERS * QGRAD_HDR + QGRAD_G2_WEIGHTS : 2];
 	if (GRAD && threadIdx.x == 0) s_g2lds = 0;
 
-	const int p = (pin >= 0) ? pin : a.p0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	const int p = a.p0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const int M = a.M, cap = a.cap;
 	const MixView vout = bank_view(a, SEL_OUT);
 	const Bank bin = bank_of(a, SEL_IN);
 	const int no = QUASI ? 0 : vout.count[p];
-	bool deferred = false;   // (workgroup-uniform) DEFER == 1: this particle is left to k_alpha_big
 	const size_t sbo = (size_t) p * cap;
 	const PoseD pose = load_pose(QUASI ? a.qposes + (size_t) p * 7 : bin.poses + (size_t) p * 7);
 
@@ -1071,7 +1061,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		}
 		for (int k = tid; k < M; k += 256) labz[k] = J + k;
 		for (int t = tid; t < MP * JW; t += 256) adjT[t] = 0;
-		if (tid == 0) { s_nroots = 0; s_big = 0; s_huge = 0; }
+		if (tid == 0) { s_nroots = 0; s_big = 0; }
 		__threadfence_block();
 		__syncthreads();
 		// detection block: defined iff Mahalanobis(z_k; h(m_j), R) < 5 (:433-442). Measurement per lane, wave w takes the
@@ -1200,7 +1190,6 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 				if (nl + nz > 5) {
 					res[ri] = NAN;   // solved below by the Murty path
 					s_big = 1;
-					if (nl + nz > ALPHA_DEFER_ROWS) s_huge = 1;
 					continue;
 				}
 				const unsigned long long Lp = pk_sort5(memL[root], nl), Zp = pk_sort5(memZ[root], nz);   // members, ascending
@@ -1288,7 +1277,6 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 					if (nrow > 5) {
 						res[ri] = NAN;   // solved below by the Murty path
 						s_big = 1;
-						if (nrow > ALPHA_DEFER_ROWS) s_huge = 1;
 					}
 					else {
 						double* mat = mats + lane;   // entry e at mat[e * 4] (fewer than 5 landmarks: at most 4 clusters)
@@ -1572,11 +1560,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 			__syncthreads();
 		}
 		PHD_STAMP(8);
-		if (DEFER == 1 && s_huge) {
-			deferred = true;
-			if (tid == 0) a.biglist[1 + atomicAdd(a.biglist, 1)] = p;   // ([0]: entries; emptied by k_normalise_resample)
-		}
-		else if ((DEFER != 1 || ALPHA_DEFER_ROWS > 5) && s_big) {   // (ALPHA_DEFER_ROWS 5: the main kernel defers every such particle and carries no solver at all)
+		if (s_big) {
 			// Some cluster has more than 5 rows: it is enumerated best-first (MurtyPairing) under the
 			// early-exit test of PHDNavigator.cs:503, which reads logcomp[m] as left behind by the clusters
 			// before it. So wave 0 replays the clusters in order up to the last such cluster, keeping the
@@ -1704,10 +1688,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 							if (!unsolved) g = pairing_gradient(colof);
 							if (lane < 6) dvec[m][lane] = g;
 						};
-						// (the step's main kernel replays clusters of at most ALPHA_DEFER_ROWS rows only: the one-row-per-lane
-						// solver, none of the frames of the two- and four-row ones)
-						if (DEFER == 1) mcount = wave_murty<1, TAG>(ws, nd, nrow, lane, hook);
-						else mcount = wave_murty_any<TAG>(ws, nd, nrow, lane, hook);
+						mcount = wave_murty_any<TAG>(ws, nd, nrow, lane, hook);
 					}
 					if (mcount >= 0) {
 						// LogSumExp(logcomp, 0, m), MatrixExtensions.cs:361-389
@@ -1961,22 +1942,20 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		// total over the components: clusters holding detections, the lone landmarks (misdetection only,
 		// log(1 - PD_j)) and the lone measurements (clutter, log kappa). The reference adds them in that order one
 		// by one; here every thread adds its share and the shares are summed in a fixed tree.
-		if (!deferred) {
-			double tpart = 0;
-			for (int r = tid; r < nroots; r += 256) tpart += res[r];
-			for (int j = tid; j < J; j += 256) {
-				bool has = false;
+		double tpart = 0;
+		for (int r = tid; r < nroots; r += 256) tpart += res[r];
+		for (int j = tid; j < J; j += 256) {
+			bool has = false;
 #pragma unroll
-				for (int b = 0; b < MW; b++) has |= adj[(size_t) j * MW + b] != 0;
-				if (!has) tpart += lmd[j];
-			}
-			for (int k = tid; k < M; k += 256) {
-				if (labz[k] == J + k) tpart += prm.logkappa;
-			}
-			__syncthreads();
-			double total = block_sum(tpart);
-			if (tid == 0) s_total = total;
+			for (int b = 0; b < MW; b++) has |= adj[(size_t) j * MW + b] != 0;
+			if (!has) tpart += lmd[j];
 		}
+		for (int k = tid; k < M; k += 256) {
+			if (labz[k] == J + k) tpart += prm.logkappa;
+		}
+		__syncthreads();
+		double total = block_sum(tpart);
+		if (tid == 0) s_total = total;
 		__syncthreads();
 	}
 	PHD_STAMP(7);
@@ -1985,7 +1964,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 #endif
 	PHD_STAMP_FLUSH(3, 12);
 	if (tid == 0) {
-		if (!deferred) a.setll[p] = s_total;
+		a.setll[p] = s_total;
 		if (!QUASI) {
 			a.aJ[p]      = J;
 			a.account[p] = s_ccount;
@@ -2002,27 +1981,8 @@ __global__ __launch_bounds__(256, PHD_ASSOC_WAVES) void k_alpha_assoc(const DevP
 	extern __shared__ __align__(16) double smem[];
 	PHD_TL_BEGIN;
 	PHD_SET_PRIO(PHD_LAT_PRIO);
-	alpha_assoc_body<ZB, false, false, 0, 0, DEPTH>(prm, a, ncap, smem);
+	alpha_assoc_body<ZB, false, false, 0, DEPTH>(prm, a, ncap, smem);
 	PHD_TL_END(3);
-}
-
-// the same with the particles that need the ordered replay (a cluster of more than 5 rows) left to k_alpha_big
-template <int ZB, bool DEPTH = false>
-__global__ __launch_bounds__(256, PHD_ASSOC_WAVES) void k_alpha_assoc_main(const DevParams prm, const StepBufs a, int ncap)
-{
-	extern __shared__ __align__(16) double smem[];
-	alpha_assoc_body<ZB, false, false, 2, 1, DEPTH>(prm, a, ncap, smem);
-}
-
-// WeightAlpha's last line for every particle (PHDNavigator.cs:390-392, :335), when k_alpha_density left it open (a.defer):
-// alpha = exp(set log-likelihood + density ratio), weight *= alpha
-__global__ __launch_bounds__(256) void k_alpha_combine(const StepBufs a)
-{
-	const int p = blockIdx.x * 256 + threadIdx.x;
-	if (p >= a.P) return;
-	const double alpha = exp(a.setll[p] + a.ratio[p]);   // :392
-	a.alpha[p] = alpha;
-	bank_of(a, SEL_OUT).weights[p] = bank_of(a, SEL_IN).weights[p] * alpha;   // :335
 }
 
 // one workgroup per candidate pose (the smoother's pose x landmark x measurement batches)
@@ -2277,14 +2237,10 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 			__hip_atomic_store(a.ratio + p, ratio, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			s_wc[0] = alpha_meet(a, p, true, ratio) ? 1 : 0;
 		}
-		else if (a.defer) a.ratio[p] = ratio;               // (k_alpha_combine: the set log-likelihood may still be in the making)
 		else {
 			double alpha = exp(a.setll[p] + ratio);         // :392
 			a.alpha[p] = alpha;
-			const double wnew = bin.weights[p] * alpha;     // :335
-			// (tickets: written through to memory — k_normalise_resample on the other stream reads it without a launch boundary between)
-			if (a.tickets) __hip_atomic_store(&bout.weights[p], wnew, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			else bout.weights[p] = wnew;
+			bout.weights[p] = bin.weights[p] * alpha;       // :335
 		}
 	}
 	if (!meet) return true;
@@ -2298,29 +2254,5 @@ __global__ __launch_bounds__(256, PHD_DENS_WAVES) void k_alpha_density(const Dev
 	PHD_TL_BEGIN;
 	PHD_SET_PRIO(PHD_DENSE_PRIO);
 	alpha_density_body(prm, a, pool);
-	// (device-side ordering of the sub-range streams, phd_step_async: thread 0 wrote the particle's weight through to memory; once
-	// that store is acknowledged it takes the ticket k_normalise_resample counts. No fence: a device-scope release would write
-	// back the XCD's whole L2 — the other stream's kernels' lines with it — 2048 times a step)
-	if (a.tickets && threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); atomicAdd(a.ticket, 1u); }
 	PHD_TL_END(4);
-}
-
-// ... and those particles, INSIDE the launch of the densities: the first `nbig` workgroups of k_alpha_density_big stride over the
-// list (how many there are is known on the device only) and run the association body again with the replay; the others are
-// k_alpha_density's. A replay is one wave deep in the solver for hundreds of microseconds: started first, beside a launch
-// that fills the machine for as long, it costs the step nothing. (On a stream of its own it did not overlap: HIP's streams
-// share four hardware queues, and with more of those the whole step ran a fifth slower.)
-template <int ZB, bool DEPTH = false>
-__global__ __launch_bounds__(256, 4) void k_alpha_density_big(const DevParams prm, const StepBufs a, int ncap, int nbig)
-{
-	extern __shared__ __align__(16) double smem[];
-	if ((int) blockIdx.x < nbig) {
-		const int n = a.biglist[0];
-		for (int w = blockIdx.x; w < n; w += nbig) {
-			alpha_assoc_body<ZB, false, false, 0, 2, DEPTH>(prm, a, ncap, smem, nullptr, a.biglist[1 + w]);
-			__syncthreads();   // (the next particle reuses the LDS arrays)
-		}
-		return;
-	}
-	alpha_density_body(prm, a, smem, a.p0 + (int) blockIdx.x - nbig);
 }

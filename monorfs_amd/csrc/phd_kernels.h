@@ -19,7 +19,7 @@
 #define PHD_FLAG_EMIT_OVERFLOW   1   // corrected components did not fit emit_capacity
 #define PHD_FLAG_J_OVERFLOW      2   // map estimate larger than the landmark scratch
 #define PHD_FLAG_BIG_CLUSTER     4   // association cluster beyond the on-device solver's cap
-#define PHD_FLAG_ORDER_TIMEOUT   8   // a kernel that orders the sub-range streams on the device gave up waiting (see k_normalise_resample, k_gate)
+#define PHD_FLAG_ORDER_TIMEOUT   8   // a wait on the device gave up: a helper workgroup of k_particle_chain for its main, or k_wait_landing for a peer's landing flag
 
 #define MIX_REC 10   // doubles per component record: w, m[3], P[6] (upper triangle)
 
@@ -126,27 +126,9 @@ struct StepBufs {
 	double* wcopy;       // [P][cap + Mcap] weight of the surviving misdetection copy of predicted component c (0: none), k_prune_merge -> k_alpha_density
 	int*    cover;       // [P][cap] 1: this pruned component is such a copy
 	double* stamps;      // [P][16] phase stamps of the diagnostic build (NULL otherwise)
-	int*    biglist;     // k_alpha_assoc_main -> k_alpha_big: [0] entries, [1 ..] the particles of this launch whose association needs the ordered replay
-	int     bigstride;   // ints between the lists of two sub-ranges
-	double* ratio;       // [P] k_alpha_density -> k_alpha_combine: the density part of log alpha
-	int     defer;       // 1: the step runs k_alpha_assoc_main / k_alpha_big / k_alpha_combine (k_alpha_density leaves alpha open)
+	double* ratio;       // [P] the density part of log alpha, left by whichever of a particle's two workgroups in k_particle_chain has it (alpha_meet)
 	int     all_pairs;   // 1: k_sweep evaluates every (component, measurement) pair, the radius gate only masks (SURVEY §8d's benchmark
 	                     // mode: the unit count P C M is exact); 0: a visit whose 64 pairs all lie outside the gate is skipped
-	// k_normalise_resample folded into the one-launch chain (small particle sets): the workgroup that takes the last ticket runs it
-	int           fold_nr;      // 1: k_particle_chain ends the step itself
-	unsigned int* ticket;       // [0] workgroups of the step's last per-particle launch(es) that are through (set back to 0 by whoever waited for them)
-	                            // [1] the number of the last step whose k_normalise_resample is through
-	int           tickets;      // 1: every workgroup of k_alpha_density publishes its weight and takes a ticket (device-side ordering of the two sub-range streams)
-	int           wait_tickets; // k_normalise_resample: 1 = wait until the ticket counter has reached ticket_target (0: the stream has ordered it)
-	unsigned int  ticket_target;// ... P times the number of device-ordered steps so far: the counter only ever grows, so tickets that arrive behind a
-	                            // timed-out wait still count for their own step and the next one's wait is not satisfied early
-	unsigned int  done_value;   // k_normalise_resample: the step number it publishes in ticket[1] when through (0: none)
-	double        nr_u;         // the arguments k_normalise_resample would have got
-	int           nr_force, nr_skip, nr_frozen;
-	int*          nr_src;
-	int*          nr_info;
-	int*          nr_sel_next;
-	int*          nr_inslot;
 	int     stamp_kernel; // which kernel writes them (env PHD_STAMP_KERNEL): 2 prune, 3 assoc, 4 density, 1 correct, 5 the one-launch chain
 	// k_particle_chain with a HELPER workgroup per particle for the densities of WeightAlpha (two workgroups per particle for that body)
 	int           dsplit;   // 1: the launch has 2 P workgroups, the second P are the helpers (2 - 4: test and measuring switches, PHD_DSPLIT_LATE)
@@ -378,7 +360,7 @@ __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, 
 		if (threadIdx.x == 0) s_hgo = 0;
 		__syncthreads();
 		PHD_STAMP(3);
-		alpha_assoc_body<ZB, false, false, 1, 0, DEPTH>(prm, a, cutcap, smem, nullptr, -1, a.dsplit ? &s_hgo : nullptr);
+		alpha_assoc_body<ZB, false, false, 1, DEPTH>(prm, a, cutcap, smem, nullptr, a.dsplit ? &s_hgo : nullptr);
 		__syncthreads();
 		PHD_STAMP(4);
 		// (every wave takes the flag into a register before thread 0 may reuse the word for alpha_meet's answer: without the
@@ -403,28 +385,6 @@ __global__ __launch_bounds__(256, 1) void k_particle_chain(const DevParams prm, 
 		PHD_STAMP(5);
 	}
 	PHD_STAMP_FLUSH(5, 6);   // (diagnostic build, PHD_STAMP_KERNEL=5: the bodies' shares of the chain)
-	}
-	if (a.fold_nr) {
-		// The end of the step without a launch of its own: behind the barrier every wave's stores have left the CU; ONE thread
-		// publishes them (release fence, device scope: the XCD's L2 is written back — by every thread that is 1024 write-backs
-		// per launch and cost more than the launch saved) and takes a ticket; the workgroup that takes the last has every
-		// particle's weight, count and flag before it (acquire fence: L1 and the L2's stale lines invalidated) and runs
-		// k_normalise_resample's body on the launch's LDS pool.
-		__shared__ int s_last;
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's stores are acknowledged by the L2
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			__threadfence();
-			const int last = ((int) atomicAdd(a.ticket + 2, 1u) == nmain - 1) ? 1 : 0;   // (a word of its own: the device order's counter beside it never goes back)
-			if (last) a.ticket[2] = 0;   // for the next launch (stream order)
-			__threadfence();
-			s_last = last;
-		}
-		__syncthreads();
-		if (s_last) {   // (workgroup-uniform)
-			normalise_resample_body(a, nullptr, a.P, prm.min_eff, a.nr_u, a.nr_force, a.nr_skip, 1, a.nr_src, a.nr_info, a.nr_sel_next,
-			                        a.nr_frozen, a.nr_inslot, smem);
-		}
 	}
 }
 
@@ -564,11 +524,6 @@ __global__ __launch_bounds__(256) void k_push_weights(const StepBufs a, double* 
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	double* w = bank_of(a, SEL_OUT).weights;
 	if (i < a.P) {
-		if (a.defer) {   // WeightAlpha's last line, left open by k_alpha_density (see k_normalise_resample)
-			const double alpha = exp(a.setll[i] + a.ratio[i]);
-			a.alpha[i] = alpha;
-			w[i] = bank_of(a, SEL_IN).weights[i] * alpha;
-		}
 		const double v = w[i];
 		for (int t = 0; t < ndst; t++) dst[t][first + i] = v;
 	}
@@ -1065,7 +1020,7 @@ __global__ __launch_bounds__(256) void k_pack_particles(const StepBufs a, const 
 // The landing flags (round 5): behind k_pack_particles on the sender's stream, one wave stores the step's number into word
 // `rank` of the flag area at the end of EVERY peer's receive buffer (fine-grained memory, system-scope release: this launch
 // begins when the pack kernel — its peer stores with it — has ended, and the fence orders whatever is still in flight
-// before the flag). The receiver's k_finish_sharded waits for the words of the ranks it takes records from: the
+// before the flag). The receiver's k_wait_landing waits for the words of the ranks it takes records from: the
 // one-word all-reduce that played landing barrier until round 4 is a second collective the step does not need.
 __global__ __launch_bounds__(64) void k_post_landing(double* const* recvbase, int n, int rank, size_t flagoff, unsigned long long seq)
 {
@@ -1078,10 +1033,10 @@ __global__ __launch_bounds__(64) void k_post_landing(double* const* recvbase, in
 }
 
 // The receiver's wait as ONE wave in front of k_finish_sharded (the default): lane t polls the word of rank t when this step
-// takes records from it; the launch boundary behind it is the acquire for everything k_finish_sharded reads. A grid that waits —
-// the same loop inside k_finish_sharded, PHD_LANDING_INLINE=1: one launch boundary (~3 us) less — holds every slot of the
-// device for as long as it waits: harmless when the senders run on OTHER devices, a standstill when ranks share one (seen:
-// four processes with 2048-particle shards on one GPU), and thousands of waves polling the memory the peers are storing into.
+// takes records from it; the launch boundary behind it is the acquire for everything k_finish_sharded reads. (The same loop inside
+// k_finish_sharded saved that boundary, ~3 us, but a grid that waits holds every slot of the device for as long as it waits: a
+// standstill when ranks share one GPU. DESIGN §6.) Bounded: landing_ticks of the 100 MHz counter, then PHD_FLAG_ORDER_TIMEOUT — a
+// peer that never posts has died.
 __global__ __launch_bounds__(64) void k_wait_landing(const MigPlan pl, int n, const unsigned long long* landing, unsigned long long seq,
                                                      long long landing_ticks, int* flags)
 {
@@ -1108,29 +1063,13 @@ __global__ __launch_bounds__(64) void k_wait_landing(const MigPlan pl, int n, co
 //     there. Block b unpacks record b (if there is one) and sets up particle b: small arrays into TMP, slot into inslot.
 //     (IN, OUT, TMP, INMIX) = (T, I, O, O)
 //   frozen: roles and slots stay (benchmark steady state); RES / RESMIX / slots say where the result is
-//   landing != NULL: the flag words of this rank's receive buffer (k_post_landing); a step that takes records from rank t waits
-//   for word t to reach `seq` — bounded (landing_ticks of the 100 MHz counter; PHD_FLAG_ORDER_TIMEOUT: a peer that never posts has died)
+//   (with landing flags, k_wait_landing in front of this launch has seen the records of the receive buffer arrive)
 __global__ __launch_bounds__(256) void k_finish_sharded(const StepBufs a, const MigPlan pl, int n, const double* recvbuf, double weight,
-                                                        int* sel_next, int frozen, int* inslot, int* slots,
-                                                        const unsigned long long* landing, unsigned long long seq, long long landing_ticks)
+                                                        int* sel_next, int frozen, int* inslot, int* slots)
 {
 	const int i = blockIdx.x, tid = threadIdx.x;
 	const int nrecv = pl.counts[2 * n + 1], status = pl.counts[2 * n + 2], resampled = pl.counts[2 * n + 3];
 	const int I = a.sel[SEL_IN], O = a.sel[SEL_OUT], T = a.sel[SEL_TMP], X = a.sel[SEL_INMIX];
-	// (the workgroups that read the receive buffer wait: the one that unpacks record i, and every particle fed by an arrival — the
-	// others, whose source is a local particle, go ahead: fewer waves polling this rank's memory while the peers' stores come in,
-	// fewer slots held by waiting workgroups)
-	if (landing && status == MIG_OK && resampled && nrecv > 0 && (i < nrecv || pl.code[i] < 0)) {   // (uniform over the workgroup)
-		if (tid < n && pl.counts[n + tid] > 0) {
-			const long long t0 = wall_clock64();
-			while ((long long) (__hip_atomic_load(landing + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - seq) < 0) {
-				if (wall_clock64() - t0 > landing_ticks) { atomicOr(a.flags, PHD_FLAG_ORDER_TIMEOUT); break; }
-				__builtin_amdgcn_s_sleep(8);
-			}
-		}
-		__syncthreads();
-		__threadfence_system();   // acquire in every wave: the records behind the flags are what the loads below see
-	}
 	if (status != MIG_OK) {
 		if (i == 0 && tid < SEL_STRIDE) sel_next[tid] = a.sel[tid];
 		return;

@@ -158,8 +158,7 @@ __device__ __forceinline__ void rotate_roles(const StepBufs& a, const int* src, 
 	}
 }
 
-// The body: the kernel's one workgroup, or — for a small particle set — the last workgroup of k_particle_chain to finish
-// (phd_kernels.h; blockDim.x = 256 there as in a launch of its own for up to 512 weights: the same tree of sums, the same bits).
+// The body of the kernel's one workgroup.
 __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, double* gw, int P, double min_eff, double u,
                                                         int force_resample, int skip_normalise, int use_lds,
                                                         int* src, int* info, int* sel_next, int frozen, int* inslot,
@@ -177,12 +176,11 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 	// (one workgroup alone on the device: every dependent trip to memory is the kernel's time. The flag word, the bank roles and
 	// this thread's first weight — from all three banks, the role picks one — are requested together: one trip instead of three)
 	double spec0 = 0, spec1 = 0, spec2 = 0;
-	const bool spec = !gw && !a.defer && tid < P;
+	const bool spec = !gw && tid < P;
 	if (spec) { spec0 = a.bank[0].weights[tid]; spec1 = a.bank[1].weights[tid]; spec2 = a.bank[2].weights[tid]; }
 	const int flags_now = sel_next ? *a.flags : 0;
 	const int sel_out = a.sel[SEL_OUT];
 	if (tid == 0 && a.bigws_used && *a.bigws_used) *a.bigws_used = 0;   // the association slab is free again (every k_alpha_assoc of the step is over)
-	if (tid < 4 && a.biglist) a.biglist[(size_t) tid * a.bigstride] = 0;   // ... and the sub-ranges' lists of deferred particles are empty again
 	// A kernel of this step raised a flag (emit capacity, landmark scratch): what it wrote into the OUT bank is not a
 	// valid state. The step is dropped as a whole — the roles stay, nothing of the current state was touched — and the host
 	// finds the flag at its next phd_sync. (Every thread reads the same word, written by earlier launches.)
@@ -191,17 +189,6 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 		return;
 	}
 	double* gwp = gw ? gw : bank_of(a, SEL_OUT).weights;
-	if (a.defer && !gw) {
-		// WeightAlpha's last line (PHDNavigator.cs:390-392, :335), left open by k_alpha_density while the set log-likelihoods of
-		// the particles with big association clusters were still in the making: alpha = exp(L + density ratio), weight *= alpha
-		const double* win = bank_of(a, SEL_IN).weights;
-		for (int i = tid; i < P; i += nt) {
-			const double alpha = exp(a.setll[i] + a.ratio[i]);
-			a.alpha[i] = alpha;
-			gwp[i] = win[i] * alpha;
-		}
-		__syncthreads();   // (a workgroup's own stores: visible to its loads behind the barrier)
-	}
 	const int CH = (P + nt - 1) / nt;              // contiguous chunk of every thread
 	const int c0 = min(P, tid * CH), c1 = min(P, c0 + CH), cn = c1 - c0;
 	// The vector is staged in LDS chunk-transposed: element j of chunk t at lw[j * LS + t], LS = nt + 1. Every loop below has
@@ -522,48 +509,11 @@ __global__ __launch_bounds__(1024) void k_normalise_resample(const StepBufs a, d
                                                              int* src, int* info, int* sel_next, int frozen, int* inslot)
 {
 	extern __shared__ __align__(16) double lw_nr[];   // [P] when use_lds
-	if (a.wait_tickets > 0) {
-		// Two sub-range streams, steps posted back to back (phd_step_async): this launch sits directly behind the k_alpha_density of
-		// ITS stream; the other stream's is ordered by count — every workgroup of both took a ticket behind a device-scope release of
-		// its weight. Everything waited for was submitted before this launch, on whatever queue; the wait is bounded (0.2 s of the
-		// 100 MHz counter: the step is then dropped with PHD_FLAG_ORDER_TIMEOUT, and so is every step behind it until phd_sync).
-		if (threadIdx.x == 0) {
-			const long long t0 = wall_clock64();
-			// (relaxed loads: an acquire per poll would invalidate the L2 under the kernels still running)
-			// (a step-stamped target on a counter that is never reset: late tickets of a step whose wait timed out cannot count towards
-			// the next step; the flag a timed-out wait raises stays up — every later step is dropped — until phd_sync has reported it)
-			while ((int) (__hip_atomic_load(a.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a.ticket_target) < 0) {
-				if (wall_clock64() - t0 > 20000000LL) { atomicOr(a.flags, PHD_FLAG_ORDER_TIMEOUT); break; }
-				__builtin_amdgcn_s_sleep(32);
-			}
-		}
-		__syncthreads();
-		__threadfence();   // acquire in every wave: what the ticket holders published is what the loads below see
-	}
 	PHD_TL_BEGIN;
 	normalise_resample_body(a, gw, P, min_eff, u, force_resample, skip_normalise, use_lds, src, info, sel_next, frozen, inslot, lw_nr);
-	if (a.done_value) {
-		// ... and the other stream's next k_sweep waits for THIS launch by number (k_gate)
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-		if (threadIdx.x == 0) { __threadfence(); __hip_atomic_store(a.ticket + 1, a.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-	}
 #ifdef PHD_STAMPS
 	if (threadIdx.x == 0 && a.stamps && a.stamp_kernel == 199) { a.stamps[8] = (double) tl0_; a.stamps[9] = (double) wall_clock64(); }
 #endif
-}
-
-// The other sub-range stream's side of that ordering: one wave in front of its next k_sweep, through when k_normalise_resample
-// number `value` is (submitted before this launch; bounded like the wait above). The launch boundary behind it is the acquire.
-__global__ __launch_bounds__(64) void k_gate(const unsigned int* done, unsigned int value, int* flags)
-{
-	if (threadIdx.x == 0) {
-		const long long t0 = wall_clock64();
-		while ((int) (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - value) < 0) {
-			if (wall_clock64() - t0 > 20000000LL) { atomicOr(flags, PHD_FLAG_ORDER_TIMEOUT); break; }
-			__builtin_amdgcn_s_sleep(64);
-		}
-	}
 }
 
 // =================================================================================================================================
@@ -645,18 +595,9 @@ __global__ __launch_bounds__(256) void k_nr_sum(const StepBufs a, double* gw, in
 	__shared__ double s4[4];
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = blockIdx.x, k = g * 256 + tid;
 	if (g == 0 && tid == 0 && a.bigws_used && *a.bigws_used) *a.bigws_used = 0;   // the association slab is free again
-	if (g == 0 && tid < 4 && a.biglist) a.biglist[(size_t) tid * a.bigstride] = 0;
 	const int flags_now = sel_next ? *a.flags : 0;   // (requested with the weights below: one trip)
 	double w = 0;
-	if (a.defer && !gw) {   // WeightAlpha's last line, left open by k_alpha_density (PHD_DEFER_BIG)
-		if (k < P) {
-			const double alpha = exp(a.setll[k] + a.ratio[k]);
-			a.alpha[k] = alpha;
-			w = bank_of(a, SEL_IN).weights[k] * alpha;
-			bank_of(a, SEL_OUT).weights[k] = w;
-		}
-	}
-	else if (graw) {
+	if (graw) {
 		if (k < P) {
 			const int r = k / Pl;
 			w = graw[(size_t) r * (Pl + 1) + (k - r * Pl)];

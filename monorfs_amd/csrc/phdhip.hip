@@ -83,24 +83,12 @@ struct phd_navigator {
 	unsigned int dseq = 0;             // launches of the chain with helpers so far (StepBufs::dstamp)
 	DevBuf<unsigned int> d_dsync;      // the helpers' words (StepBufs); DSPLIT_ROWS particles
 	int         chain_max = 512;       // up to this many particles a step's per-particle kernels run as one launch (k_particle_chain; env PHD_CHAIN_MAX)
-	int         fold_nr = 0;           // 1 (env PHD_FOLD_NR): the chain ends the step itself — k_normalise_resample's body in its last workgroup; measured slower than the launch
 	bool        chain_ok[3] = {false, false, false};   // ... where the bodies' LDS arrays fit one workgroup (per measurement-block count 1, 2, 4)
 	Stream      aux[MAXSPLIT - 1];     // streams of the sub-ranges after the first
-	// Option (environment PHD_DEFER_BIG=1; off by default): the particles with an association cluster of more than
-	// ALPHA_DEFER_ROWS rows are listed by k_alpha_assoc_main and their ordered replay runs inside the launch of the densities
-	// (the first workgroups of k_alpha_density_big), k_normalise_resample / k_push_weights finish alpha. Built when the replay
-	// was what config S's association kernel waited for (5 % of the particles, 15 times the median workgroup's lifetime); since
-	// the clusters of up to 5 rows are no longer replayed one by one (phd_alpha.h, apply_small) the replay is short and the
-	// option costs more than it hides (config S 3.80 against 3.62 ms: the fused launch needs the association's LDS, three
-	// workgroups per CU for the densities instead of four). Kept for scenes whose clusters are large; bit-identical results.
-	int         defer_big = 0;
-	int         nbig = 256;            // workgroups of k_alpha_density_big that work the list off (environment PHD_NBIG)
 	int         fuse_ep = -1;          // k_emit_finish and k_prune_merge as one launch (k_emit_prune): -1 = for frames of up to 64 measurements (measured on
 	                                   // two streams: config B 0.677 -> 0.667 ms survey, 0.634 -> 0.615 steady; config S, 128 measurements, 3.67 -> 3.85:
 	                                   // its Kalman path is long and pays for the 128 registers); environment PHD_FUSE_EP = 0 / 1 forces
-	int         last_defer = 0;        // the last launch_map left alpha open (k_normalise_resample / k_push_weights / k_alpha_combine finish it)
-	DevBuf<int>    d_biglist;          // [MAXSPLIT][Pcap + 2]
-	DevBuf<double> d_ratio;            // [Pcap]
+	DevBuf<double> d_ratio;            // [Pcap] StepBufs::ratio
 	Event       ev_fork, ev_join[MAXSPLIT - 1];
 	// Two sub-ranges, steps posted back to back (phd_step_async after phd_step_async): the end of the step runs on the stream
 	// whose chain finishes LAST and no fork precedes the next step ("the step boundary"; env PHD_PIPELINE=0: a fork
@@ -109,11 +97,6 @@ struct phd_navigator {
 	bool        pipe_ok = false;       // nothing was enqueued on `stream` since the last such step: the aux stream is ordered behind all of it
 	int         lagger = 1;            // which of the two streams (0 `stream`, 1 aux[0]) finishes the coming step last
 	Event       ev_res;                // k_normalise_resample is through (recorded on the stream that ran it)
-	int         device_order = 0;      // 1 (env PHD_DEVICE_ORDER): between such steps no event at all — k_normalise_resample counts the tickets of both
-	                                   // streams' k_alpha_density workgroups, the other stream's next k_sweep waits behind k_gate. Measured 0.2 % faster
-	                                   // than the events; two kernels that poll are not worth that by default
-	unsigned    step_seq = 0;          // number of the last step ended that way
-	unsigned    ticket_total = 0;      // tickets all such steps so far have handed out (P per step): what k_normalise_resample waits for — the counter is never reset
 	bool sel_host_valid = false;       // h_sel mirrors the device-side bank roles without a round trip
 	int Pcap = 0, cap = 0, Mcap = 0, ecap = 0, Jcap = 0, cutcap = 0;
 	int P = 0, M = 0;
@@ -188,7 +171,6 @@ struct phd_navigator {
 	bool recv_finegrained = false;                   // d_recv is fine-grained device memory (coherent for the peers that store into it)
 	int  landing_flags = 0;                          // phd_migration_set_landing: 1 = push posts step-stamped flags into the peers' receive buffers, unpack waits for them
 	unsigned long long landing_seq = 0;              // number of the last device-path global step (the flags' stamp)
-	int       landing_inline = 0;                    // 1 (PHD_LANDING_INLINE): the wait inside k_finish_sharded instead of k_wait_landing in front of it
 	long long landing_ticks = 1000000000LL;          // bound of the wait for a flag, in ticks of the 100 MHz counter: 10 s (environment PHD_LANDING_TIMEOUT_MS)
 	DevBuf<double> d_graw; int grawcap = 0;          // per-rank host: the all-gather's landing buffer, [world][P + 1] (weights | status word)
 	std::vector<void*> ipc_opened;                   // peers' receive buffers opened with hipIpcOpenMemHandle (closed in phd_destroy)
@@ -309,12 +291,10 @@ StepBufs make_bufs(phd_navigator* nav)
 	b.born_count = nav->d_born_count; b.born_k = nav->d_born_k; b.born_mean = nav->d_born_mean;
 	b.alpha = nav->d_alpha; b.setll = nav->d_setll; b.flags = nav->d_flags; b.murty = nav->d_murty; b.jscratch = nav->d_jscratch;
 	b.bigws = nav->d_bigws; b.bigws_bytes = nav->bigws_bytes; b.bigws_used = nav->d_bigws_used;
-	b.fold_nr = 0; b.ticket = (unsigned int*) (nav->d_bigws_used + 1); b.tickets = 0; b.wait_tickets = 0; b.ticket_target = 0; b.done_value = 0;
-	b.nr_u = 0; b.nr_force = 0; b.nr_skip = 0; b.nr_frozen = 0; b.nr_src = nullptr; b.nr_info = nullptr; b.nr_sel_next = nullptr; b.nr_inslot = nullptr;
 	b.cand_count = nav->d_cand_count; b.denom = nav->d_denom;
 	b.cand = nav->d_cand; b.candcap = nav->candcap;
 	b.dsplit = 0; b.dstamp = 0; b.dsync = nav->d_dsync;
-	b.alm = nav->d_alm; b.aJ = nav->d_aJ; b.account = nav->d_account; b.srec = nav->d_srec; b.outw = nav->d_outw; b.wcopy = nav->d_wcopy; b.cover = nav->d_cover; b.stamps = nav->d_stamps; b.biglist = nav->d_biglist; b.bigstride = nav->Pcap + 2; b.ratio = nav->d_ratio; b.defer = 0; b.all_pairs = nav->all_pairs ? 1 : 0; b.stamp_kernel = getenv("PHD_STAMP_KERNEL") ? atoi(getenv("PHD_STAMP_KERNEL")) : 2;
+	b.alm = nav->d_alm; b.aJ = nav->d_aJ; b.account = nav->d_account; b.srec = nav->d_srec; b.outw = nav->d_outw; b.wcopy = nav->d_wcopy; b.cover = nav->d_cover; b.stamps = nav->d_stamps; b.ratio = nav->d_ratio; b.all_pairs = nav->all_pairs ? 1 : 0; b.stamp_kernel = getenv("PHD_STAMP_KERNEL") ? atoi(getenv("PHD_STAMP_KERNEL")) : 2;
 	return b;
 }
 
@@ -429,15 +409,12 @@ struct StepVariant {
 	void (*emit_prune)(DevParams, StepBufs, int);
 	void (*emit_finish)(DevParams, StepBufs);
 	void (*assoc)(DevParams, StepBufs, int);
-	void (*assoc_main)(DevParams, StepBufs, int);
-	void (*density_big)(DevParams, StepBufs, int, int);
 	void (*quasi)(DevParams, StepBufs, int);
 	void (*quasi_grad)(DevParams, StepBufs, int);
 	int  (*chain_pool)(int);
 	int zi() const { return zb >> 1; }   // index of ZB = 1, 2, 4 (phd_navigator::chain_ok)
 	int chain_lds(int cutcap) const { return chain_pool(cutcap); }
 	int assoc_lds(int cutcap) const { return alpha_lds(zb * 64, cutcap).bytes; }
-	int density_big_lds(int cutcap) const { return std::max(assoc_lds(cutcap), (int) (DENS_LDS_DOUBLES * 8)); }   // the larger of the two bodies' pools
 	static int emit_prune_lds(int cutcap) { return std::max((int) prune_lds(cutcap).bytes, (int) (EMIT_LDS_DOUBLES * 8)); }
 };
 
@@ -445,7 +422,7 @@ template <int ZB, bool HALF, bool DEPTH>
 StepVariant make_variant()
 {
 	return {ZB, HALF, DEPTH, k_particle_chain<ZB, HALF, DEPTH>, k_sweep<ZB, HALF, DEPTH>, k_emit_prune<DEPTH>, k_emit_finish<DEPTH>, k_alpha_assoc<ZB, DEPTH>,
-	        k_alpha_assoc_main<ZB, DEPTH>, k_alpha_density_big<ZB, DEPTH>, k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, chain_lds_bytes<ZB>};
+	        k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, chain_lds_bytes<ZB>};
 }
 
 const StepVariant step_variants[8] = {make_variant<1, false, false>(), make_variant<1, true, false>(), make_variant<2, false, false>(), make_variant<4, false, false>(),
@@ -494,21 +471,16 @@ int launch_map(phd_navigator* nav, const StepBufs& b0, bool with_alpha, int pipe
 		}
 		launch_timed(nav, T_CH, nav->stream, false, v.chain, dim3(helpers ? 2 * P : P), block, (size_t) v.chain_lds(cutcap), nav->dp, bc, cutcap, wa);
 		HC(hipGetLastError());
-		nav->last_defer = 0;
 		return PHD_OK;
 	}
 	if (S > 1 && pipe < 0) {
 		HC(hipEventRecord(nav->ev_fork, nav->stream));
 		for (int s = 1; s < S; s++) HC(hipStreamWaitEvent(nav->aux[s - 1], nav->ev_fork, 0));
 	}
-	const bool defer = with_alpha && nav->defer_big != 0;
-	nav->last_defer = defer ? 1 : 0;
 	const size_t la = (size_t) v.assoc_lds(cutcap);
 	for (int si = 0; si < S; si++) {
 		const int s = (pipe >= 0 && S == 2) ? (si == 0 ? 1 - pipe : pipe) : si;
 		StepBufs b = b0;
-		b.defer = defer ? 1 : 0;
-		b.biglist = nav->d_biglist + (size_t) s * b0.bigstride;
 		b.p0 = (int) ((long long) P * s / S);
 		const int n = (int) ((long long) P * (s + 1) / S) - b.p0;
 		if (n <= 0) continue;
@@ -522,13 +494,7 @@ int launch_map(phd_navigator* nav, const StepBufs& b0, bool with_alpha, int pipe
 			launch_timed(nav, T_EF, st, true, v.emit_finish, grid, block, 0, nav->dp, b);
 			launch_timed(nav, T_PM, st, true, k_prune_merge, grid, block, lp, nav->dp, b, cutcap);
 		}
-		if (with_alpha && defer) {
-			launch_timed(nav, T_WA, st, true, v.assoc_main, grid, block, la, nav->dp, b, cutcap);
-			// the particles it listed are worked off by the first workgroups of the densities' launch
-			const int nbig = std::max(1, std::min(nav->nbig, n));
-			launch_timed(nav, T_WD, st, true, v.density_big, dim3(n + nbig), block, (size_t) v.density_big_lds(cutcap), nav->dp, b, cutcap, nbig);
-		}
-		else if (with_alpha) {
+		if (with_alpha) {
 			launch_timed(nav, T_WA, st, true, v.assoc, grid, block, la, nav->dp, b, cutcap);
 			launch_timed(nav, T_WD, st, true, k_alpha_density, grid, block, 0, nav->dp, b);
 		}
@@ -558,7 +524,7 @@ int launch_normalise(phd_navigator* nav, const StepBufs& b, double* gw, int P, d
                      const PlanGrid* pgp = nullptr, int rank = 0, const double* gflags = nullptr, bool* counted = nullptr)
 {
 	if (!st) st = nav->stream;
-	if (nav->nr_grid_min > 0 && P >= nav->nr_grid_min && P <= 65536 && b.wait_tickets == 0 && b.done_value == 0) {
+	if (nav->nr_grid_min > 0 && P >= nav->nr_grid_min && P <= 65536) {
 		// one particle per thread over a grid, four launches (phd_resample.h, "over a GRID"): 16 384 weights in ~15 us instead of 48
 		if (P > nav->nrcap) {
 			HC(hipDeviceSynchronize());   // (first use, or a longer vector than ever before: rare)
@@ -590,8 +556,7 @@ int launch_normalise(phd_navigator* nav, const StepBufs& b, double* gw, int P, d
 	}
 	if (graw) hipLaunchKernelGGL(k_ungather, dim3((P + world + 255) / 256), dim3(256), 0, st, graw, gw, Pl, world);
 	// one workgroup; 256 / 512 threads for shorter weight vectors (fewer waves to meet at every barrier), 1024 beyond 4096
-	static const int nr_env = getenv("PHD_NR_THREADS") ? atoi(getenv("PHD_NR_THREADS")) : 0;
-	const int nthreads = (nr_env == 256 || nr_env == 512 || nr_env == 1024) ? nr_env : (P <= 512 ? 256 : (P <= 4096 ? 512 : 1024));
+	const int nthreads = P <= 512 ? 256 : (P <= 4096 ? 512 : 1024);
 	// the weight vector is staged in LDS (chunk-transposed: a whole chunk per thread, used or not) when it fits beside the
 	// kernel's static arrays (160 KB per CU); above that the kernel works on the vector in global memory
 	size_t lds = (size_t) ((P + nthreads - 1) / nthreads) * (nthreads + 1) * 8;
@@ -613,7 +578,7 @@ int check_flags(phd_navigator* nav)
 		return nav->fail(PHD_ERR_CAPACITY, "map estimate larger than the landmark scratch (" + std::to_string(nav->Jcap) + ")");
 	}
 	if (f & PHD_FLAG_ORDER_TIMEOUT) {
-		return nav->fail(PHD_ERR_GENERIC, "a kernel gave up a bounded wait on the device: for work of the handle's other stream submitted before it (PHD_DEVICE_ORDER=1: 0.2 s; "
+		return nav->fail(PHD_ERR_GENERIC, "a kernel gave up a bounded wait on the device: a helper workgroup of the one-launch chain for its particle's main workgroup (2 s; "
 		                 "the step was dropped, the state is the one before it), or for the landing flag of a peer's migrating particles (phd_migration_set_landing: "
 		                 "PHD_LANDING_TIMEOUT_MS; a rank has died, the state of this handle is undefined)");
 	}
@@ -858,16 +823,12 @@ phd_navigator* phd_create(const phd_params* params, int device)
 	ok = ok && ev_create(nav->ev_fork.put(), hipEventDisableTiming);
 	ok = ok && ev_create(nav->ev_res.put(), evflags);
 	if (const char* e = getenv("PHD_PIPELINE")) nav->pipeline = atoi(e) != 0;
-	if (const char* e = getenv("PHD_DEVICE_ORDER")) nav->device_order = atoi(e) != 0;
-	if (const char* e = getenv("PHD_DEFER_BIG")) nav->defer_big = atoi(e) != 0;
 	if (const char* e = getenv("PHD_FUSE_EP")) nav->fuse_ep = atoi(e) != 0 ? 1 : 0;
-	if (const char* e = getenv("PHD_NBIG")) nav->nbig = std::max(1, atoi(e));
 	if (const char* e = getenv("PHD_SPLIT")) nav->nsplit = std::max(0, atoi(e));
 	if (const char* e = getenv("PHD_CHAIN_MAX")) nav->chain_max = std::max(0, atoi(e));
 	if (const char* e = getenv("PHD_DSPLIT_MAX")) nav->dsplit_max = std::max(0, atoi(e));
 	if (const char* e = getenv("PHD_DSPLIT_LATE")) nav->dsplit_late = atoi(e);
 	if (const char* e = getenv("PHD_DSPLIT_SEQ0")) nav->dseq = (unsigned int) std::max(0LL, atoll(e));   // (tests: launch numbers that start again soon)
-	if (const char* e = getenv("PHD_FOLD_NR")) nav->fold_nr = atoi(e) != 0;
 	if (const char* e = getenv("PHD_NR_GRID_MIN")) nav->nr_grid_min = std::max(0, atoi(e));
 	if (const char* e = getenv("PHD_PLAN_GRID_MIN")) nav->plan_grid_min = std::max(0, atoi(e));
 	size_t plane = (size_t) nav->Pcap * nav->cap;
@@ -899,8 +860,8 @@ phd_navigator* phd_create(const phd_params* params, int device)
 	ok = ok && dalloc(nav->d_src, (size_t) nav->Pcap * 4);
 	ok = ok && dalloc(nav->d_murty, (size_t) nav->Pcap * sizeof(MurtyNodes));
 	nav->bigws_bytes = 128ull << 20;
-	ok = ok && dalloc(nav->d_bigws, nav->bigws_bytes) && dalloc(nav->d_bigws_used, 32);   // [0] the slab's bump counter; 32-bit words behind it: the device order's ticket counter (never reset) and step number, the chain's own ticket
-	if (ok) hipMemset(nav->d_bigws_used, 0, 32);
+	ok = ok && dalloc(nav->d_bigws, nav->bigws_bytes) && dalloc(nav->d_bigws_used, 8);   // the slab's bump counter
+	if (ok) hipMemset(nav->d_bigws_used, 0, 8);
 	nav->cmcap = nav->cap + nav->Mcap;
 	ok = ok && dalloc(nav->d_cand_count, (size_t) nav->Pcap * 4 * 4) && dalloc(nav->d_denom, (size_t) nav->Pcap * nav->Mcap * 8);
 	nav->candcap = 16 * nav->cmcap;   // a quarter of all pairs at 64 measurements (four wave segments); beyond it the full second sweep runs
@@ -910,8 +871,7 @@ phd_navigator* phd_create(const phd_params* params, int device)
 #endif
 	ok = ok && dalloc(nav->d_srec, (size_t) nav->Pcap * PRUNE_ROW * nav->cutcap * 8);
 	ok = ok && dalloc(nav->d_outw, plane * 8);
-	ok = ok && dalloc(nav->d_biglist, (size_t) phd_navigator::MAXSPLIT * (nav->Pcap + 2) * 4) && dalloc(nav->d_ratio, (size_t) nav->Pcap * 8);
-	if (ok) hipMemset(nav->d_biglist, 0, (size_t) phd_navigator::MAXSPLIT * (nav->Pcap + 2) * 4);
+	ok = ok && dalloc(nav->d_ratio, (size_t) nav->Pcap * 8);
 	ok = ok && dalloc(nav->d_wcopy, (size_t) nav->Pcap * (nav->cap + nav->Mcap) * 8) && dalloc(nav->d_cover, (size_t) nav->Pcap * nav->cap * 4);
 	ok = ok && dalloc(nav->d_alm, (size_t) nav->Pcap * 3 * nav->Jcap * 8);
 	ok = ok && dalloc(nav->d_aJ, (size_t) nav->Pcap * 4) && dalloc(nav->d_account, (size_t) nav->Pcap * 8);
@@ -947,8 +907,6 @@ phd_navigator* phd_create(const phd_params* params, int device)
 			const int la = v.assoc_lds(cutcap);
 			if (la > lim.alpha[i]) {
 				raise(v.assoc, la);
-				raise(v.assoc_main, la);
-				raise(v.density_big, v.density_big_lds(cutcap));
 				raise(v.quasi, la);
 				raise(v.quasi_grad, la);
 				lim.alpha[i] = la;
@@ -1454,15 +1412,6 @@ int phd_set_all_pairs(phd_navigator* nav, uint8_t all_pairs)
 	return PHD_OK;
 }
 
-// Does a step of this handle run as the one-launch chain (launch_map), and may that launch end the step itself?
-static bool chain_folds_normalise(const phd_navigator* nav)
-{
-	const StepVariant& v = variant(nav->M, nav->dp.depth != nullptr);
-	if (!nav->fold_nr || !nav->chain_ok[v.zi()] || nav->P > nav->chain_max) return false;
-	const size_t lw = (size_t) ((nav->P + 255) / 256) * 257 * 8;   // the weight vector, chunk-transposed, in the chain's pool
-	return lw <= (size_t) v.chain_lds(nav->cutcap);
-}
-
 int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 {
 	if (!nav) return PHD_ERR_BAD_ARGUMENT;
@@ -1472,12 +1421,6 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 	nav->timing_now = (nav->timing_step++ % nav->timing_period) == 0;
 	StepBufs b = make_bufs(nav);
 	nav->d_res_slots = nav->d_src;
-	const bool folded = chain_folds_normalise(nav);
-	if (folded) {
-		// a small particle set: the chain's last workgroup normalises, resamples and rotates the roles (no launch of its own)
-		b.fold_nr = 1; b.nr_u = u_resample; b.nr_force = onlymapping ? -1 : 0; b.nr_skip = onlymapping ? 1 : 0; b.nr_frozen = nav->frozen ? 1 : 0;
-		b.nr_src = nav->d_src; b.nr_info = nav->d_info; b.nr_sel_next = nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE; b.nr_inslot = nav->d_inslot;
-	}
 	// The step boundary with two sub-range streams. A fork before the step and a join behind it put two markers and a barrier
 	// between the last k_alpha_density and k_normalise_resample, and one more between that and the next k_sweep: 22 + 21 us in
 	// which the device runs nothing (scripts/timeline_step.py). Posted back to back, the steps need neither: the stream whose
@@ -1496,38 +1439,18 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 			nav->lagger = 1;
 		}
 		hipStream_t L = nav->lagger ? nav->aux[0] : nav->stream, X = nav->lagger ? nav->stream : nav->aux[0];
-		// (on the device: a localising step whose densities run as k_alpha_density — that kernel's workgroups take the tickets)
-		const bool dev = nav->device_order && !onlymapping && !nav->defer_big;
-		b.tickets = dev ? 1 : 0;
 		rc = launch_map(nav, b, !onlymapping, nav->lagger);
 		if (rc) { nav->pipe_ok = false; return rc; }
-		b.defer = nav->last_defer;
-		if (dev) {
-			nav->step_seq++;
-			if (nav->step_seq == 0) nav->step_seq = 1;
-			nav->ticket_total += (unsigned) nav->P;
-			b.wait_tickets = 1;
-			b.ticket_target = nav->ticket_total;
-			b.done_value = nav->step_seq;
-		}
-		else {
-			HC(hipEventRecord(nav->ev_join[0], X));
-			HC(hipStreamWaitEvent(L, nav->ev_join[0], 0));
-		}
+		HC(hipEventRecord(nav->ev_join[0], X));
+		HC(hipStreamWaitEvent(L, nav->ev_join[0], 0));
 		{
 			Timed t(nav, T_NR, L);
 			rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
 			                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE, L);
 		}
 		if (rc) { nav->pipe_ok = false; return rc; }
-		if (dev) {
-			hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, X, b.ticket + 1, nav->step_seq, nav->d_flags);
-			HC(hipGetLastError());
-		}
-		else {
-			HC(hipEventRecord(nav->ev_res, L));
-			HC(hipStreamWaitEvent(X, nav->ev_res, 0));
-		}
+		HC(hipEventRecord(nav->ev_res, L));
+		HC(hipStreamWaitEvent(X, nav->ev_res, 0));
 		nav->lagger ^= 1;
 		nav->pipe_ok = true;
 	}
@@ -1535,16 +1458,13 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 		nav->pipe_ok = false;
 		rc = launch_map(nav, b, !onlymapping);
 		if (rc) return rc;
-		if (!folded) {
-			b.defer = nav->last_defer;
-			{
-				Timed t(nav, T_NR, nav->stream);
-				// the same launch hands the resampled particles their small arrays and rotates the bank roles (rotate_roles)
-				rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
-				                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE);
-			}
-			if (rc) return rc;
+		{
+			Timed t(nav, T_NR, nav->stream);
+			// the same launch hands the resampled particles their small arrays and rotates the bank roles (rotate_roles)
+			rc = launch_normalise(nav, b, nullptr, nav->P, u_resample, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_src, nav->d_info,
+			                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE);
 		}
+		if (rc) return rc;
 	}
 	nav->parity ^= 1;
 	nav->stage_valid = false;
@@ -1661,14 +1581,9 @@ int phd_stage_run(phd_navigator* nav, const double* z3, int nmeasurements, uint8
 	HC(hipMemsetAsync(nav->d_bigws_used, 0, 8, nav->stream));
 	rc = launch_map(nav, b, with_alpha != 0);
 	if (rc) return rc;
-	if (nav->last_defer) {   // (no k_normalise_resample follows a stage run: alpha is finished here)
-		b.defer = 1;
-		hipLaunchKernelGGL(k_alpha_combine, dim3((nav->P + 255) / 256), dim3(256), 0, nav->stream, b);
-	}
 	hipLaunchKernelGGL(k_expand_emit, dim3(nav->P), dim3(256), 0, nav->stream, nav->dp, b);   // PHD_STAGE_CORRECTED reads whole records
 	HC(hipGetLastError());
 	HC(hipMemsetAsync(nav->d_bigws_used, 0, 8, nav->stream));   // (as behind a quasi batch: no k_normalise_resample follows a stage run)
-	for (int s_ = 0; s_ < phd_navigator::MAXSPLIT; s_++) HC(hipMemsetAsync(nav->d_biglist + (size_t) s_ * (nav->Pcap + 2), 0, 4, nav->stream));
 	rc = sync_state(nav);
 	if (rc) return rc;
 	nav->stage_valid = true;
@@ -1992,7 +1907,6 @@ static int step_local(phd_navigator* nav, uint8_t onlymapping)
 	StepBufs b = make_bufs(nav);
 	rc = launch_map(nav, b, !onlymapping);
 	if (rc) return rc;
-	b.defer = nav->last_defer;
 	// (per-rank host: the export buffer holds P + 1 doubles, the step's status word behind the weights)
 	launch_timed(nav, T_PW, nav->stream, false, k_push_weights, dim3((nav->P + 255) / 256), dim3(256), 0, b, (double* const*) nav->d_dst_tab, nav->ndst,
 	             nav->push_first, nav->gw_shared ? nav->push_flagslot : nav->P);
@@ -2170,7 +2084,6 @@ int phd_migration_set_landing(phd_navigator* nav, int flags)
 	HC(hipStreamSynchronize(nav->stream));
 	nav->landing_flags = flags ? 1 : 0;
 	if (const char* e = getenv("PHD_LANDING_TIMEOUT_MS")) nav->landing_ticks = std::max(1LL, atoll(e)) * 100000LL;
-	if (const char* e = getenv("PHD_LANDING_INLINE")) nav->landing_inline = atoi(e) != 0;
 	return PHD_OK;
 }
 
@@ -2469,17 +2382,13 @@ static int step_finish(phd_navigator* nav)
 	nav->d_res_slots = nav->d_mslot;
 	{
 		Timed t(nav, T_GR, nav->stream);
-		const unsigned long long* landing = nullptr;
-		if (nav->landing_flags && nav->plan_on_device && nav->world > 1) {
+		if (nav->landing_flags && nav->plan_on_device && nav->world > 1) {   // one wave waits, in front of the launch that reads
 			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
-			landing = (const unsigned long long*) (nav->d_recv + (size_t) nav->recvrecs * rec);
-			if (!nav->landing_inline) {   // one wave waits, in front of the launch that reads (k_wait_landing)
-				hipLaunchKernelGGL(k_wait_landing, dim3(1), dim3(64), 0, nav->stream, nav->plan, nav->world, landing, nav->landing_seq, nav->landing_ticks, nav->d_flags);
-				landing = nullptr;
-			}
+			const unsigned long long* landing = (const unsigned long long*) (nav->d_recv + (size_t) nav->recvrecs * rec);
+			hipLaunchKernelGGL(k_wait_landing, dim3(1), dim3(64), 0, nav->stream, nav->plan, nav->world, landing, nav->landing_seq, nav->landing_ticks, nav->d_flags);
 		}
 		hipLaunchKernelGGL(k_finish_sharded, dim3(nav->P), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (const double*) nav->d_recv,
-		                   1.0 / (double) nav->last_world_particles, sel_next, nav->frozen ? 1 : 0, nav->d_inslot, nav->d_mslot, landing, nav->landing_seq, nav->landing_ticks);
+		                   1.0 / (double) nav->last_world_particles, sel_next, nav->frozen ? 1 : 0, nav->d_inslot, nav->d_mslot);
 	}
 	HC(hipGetLastError());
 	nav->parity ^= 1;

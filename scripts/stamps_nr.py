@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: phase stamps of k_normalise_resample (one workgroup; -DPHD_STAMPS build, PHD_STAMP_KERNEL=6: it leaves its
-stamps in row 0 of the slab behind k_sweep's). Usage on the GPU box: PHD_STAMP_SHAPE=256,128,32 PHD_FOLD_NR=0 python scripts/stamps_nr.py steady"""
+stamps in row 0 of the slab behind k_sweep's). Usage on the GPU box: PHD_STAMP_SHAPE=256,128,32 python scripts/stamps_nr.py steady"""
 import ctypes as C
 import os
 import subprocess

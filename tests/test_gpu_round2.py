@@ -338,25 +338,44 @@ def test_association_workspace_exhausted_is_an_error_that_keeps_the_state(nav_mo
     nav.close()
 
 
-def test_one_launch_chain_equals_the_separate_kernels(nav_mod, monkeypatch):
+# (particles, components, measurements), frame seed, weight profile, plan of steps:
+#   "perturbed"  three localising steps on perturbed measurements
+#   "five"       five steps on the frame's measurements, resampled and not, the fourth mapping-only
+CHAIN_CASES = [((40, 90, 20), 321, "steady", "perturbed"), ((256, 128, 32), 1002, "steady", "five"), ((256, 128, 32), 1002, "survey", "five"),
+               ((96, 40, 20), 1002, "steady", "five"), ((512, 64, 70), 1002, "steady", "five")]
+
+
+@pytest.mark.parametrize("shape,seed,profile,plan", CHAIN_CASES, ids=["%dx%dx%d-%s-%s" % (c[0] + (c[2], c[3])) for c in CHAIN_CASES])
+def test_one_launch_chain_equals_the_separate_kernels(nav_mod, monkeypatch, shape, seed, profile, plan):
     """Small particle sets run predict / correct / prune / reweight as one launch (k_particle_chain: the five kernels'
     bodies back to back in the particle's workgroup); the same steps through the five separate launches must give the
-    same bits."""
-    f = Frame(40, 90, 20, 321, weight_profile="steady")
-    rng = np.random.default_rng(9)
-    zs = [f.z + rng.normal(size=f.z.shape) * np.sqrt([2.0, 2.0, 1e-3]) * 0.3 for _ in range(3)]
+    same bits: weights, resampling sources and decision, BestParticle and maps after every step. The shapes take every
+    build of the chain the step picks by measurement count (up to 32, up to 64, 70: two measurement blocks), with and
+    without helper workgroups (up to 256 particles)."""
+    f = Frame(shape[0], shape[1], shape[2], seed, weight_profile=profile)
+    if plan == "perturbed":
+        rng = np.random.default_rng(9)
+        steps = [(f.z + rng.normal(size=f.z.shape) * np.sqrt([2.0, 2.0, 1e-3]) * 0.3, 0.2 + 0.3 * k, False) for k in range(3)]
+    else:
+        steps = [(f.z, u, k == 3) for k, u in enumerate((0.3, 0.8, 0.05, 0.6, 0.95))]
 
     def run(chain_max):
         monkeypatch.setenv("PHD_CHAIN_MAX", str(chain_max))
         nav, _ = make_nav(nav_mod, f)
         out = []
-        for k, z in enumerate(zs):
-            nav.SlamUpdate(None, z, u_resample=0.2 + 0.3 * k)
-            out.append((nav.VehicleWeights, nav.resample_sources(), nav.BestParticle, [nav.MapModel(i) for i in (0, 13, 39)]))
+        for z, u, onlymapping in steps:
+            nav.OnlyMapping = onlymapping
+            nav.SlamUpdate(None, z, u_resample=u)
+            src, resampled = nav.resample_sources()
+            out.append((nav.VehicleWeights.copy(), (np.array(src).copy(), resampled), nav.BestParticle,
+                        [nav.MapModel(i) for i in sorted({0, 13, f.P // 2, f.P - 1})]))
         nav.close()
         return out
 
-    for (wa, sa, ba, ma), (wb, sb, bb, mb) in zip(run(0), run(1000)):
+    separate, chain = run(0), run(1000)
+    if plan == "five" and profile == "steady":
+        assert any(s[1][1] for s in chain)   # (the resampling branch was taken)
+    for (wa, sa, ba, ma), (wb, sb, bb, mb) in zip(separate, chain):
         assert np.array_equal(wa, wb) and np.array_equal(sa[0], sb[0]) and sa[1] == sb[1] and ba == bb
         for x, y in zip(ma, mb):
             assert all(np.array_equal(u, v) for u, v in zip(x, y))

@@ -422,12 +422,10 @@ def test_landing_flags_are_refused_on_ordinary_receive_buffers(nav_mod, monkeypa
     nav.close()
 
 
-@pytest.mark.parametrize("inline", ["0", "1"])
-def test_landing_wait_in_its_own_wave_and_inside_the_unpack_kernel(nav_mod, monkeypatch, inline):
-    """the two places of the receiver's wait (k_wait_landing in front of k_finish_sharded, the default; PHD_LANDING_INLINE=1: inside
-    its workgroups) give the same sharded steps, bit for bit the single handle"""
+def test_landing_wait_in_its_own_wave_gives_the_single_handles_steps(nav_mod):
+    """the receiver's wait for the landing flags (k_wait_landing, one wave in front of k_finish_sharded) gives the same sharded
+    steps, bit for bit the single handle"""
     from test_gpu_round4 import _device_path_handles, _device_path_step
-    monkeypatch.setenv("PHD_LANDING_INLINE", inline)
     world, Pl, Cc, M = 3, 64, 70, 18
     f = _depleted_frame(world, Pl, Cc, M, 5500)
     p1 = prm3d_defaults(max_particles=Pl * world, max_components=600, max_measurements=M)
@@ -466,12 +464,10 @@ def test_helper_workgroups_of_the_chain_change_no_bit(nav_mod, monkeypatch, shap
     P, Cc, M, prof = shape
     f = Frame(P, Cc, M, 511, weight_profile=prof)
     got = {}
-    for mode in ("helpers", "again", "late", "unpicked", "off", "other-end", "numbers-start-again"):
+    for mode in ("helpers", "again", "late", "unpicked", "off", "numbers-start-again"):
         monkeypatch.setenv("PHD_DSPLIT_MAX", "0" if mode == "off" else "256")
         # (the launches' numbers are 27 bits long: the handle of the last mode starts two launches short of their end)
         monkeypatch.setenv("PHD_DSPLIT_SEQ0", str(0x07ffffff - 3) if mode == "numbers-start-again" else "0")
-        if mode == "other-end":   # the step's end inside the chain's launch (PHD_FOLD_NR=1; the default is a launch behind it): the finishers' count
-            monkeypatch.setenv("PHD_FOLD_NR", "1")
         monkeypatch.setenv("PHD_DSPLIT_LATE", {"late": "1", "unpicked": "3"}.get(mode, "0"))
         nav, p = _handle(nav_mod, f)
         nav.run_stages(f.z)               # (the stages of one update, for WeightAlpha's values themselves; the state stays)
@@ -488,9 +484,8 @@ def test_helper_workgroups_of_the_chain_change_no_bit(nav_mod, monkeypatch, shap
             assert np.array_equal(got[mode][1], src)
             assert np.allclose(got[mode][0], st.weights, rtol=1e-6, atol=1e-300)
         nav.close()
-    monkeypatch.delenv("PHD_FOLD_NR", raising=False)
     monkeypatch.delenv("PHD_DSPLIT_SEQ0", raising=False)
-    for mode in ("again", "late", "unpicked", "off", "other-end", "numbers-start-again"):
+    for mode in ("again", "late", "unpicked", "off", "numbers-start-again"):
         assert np.array_equal(got[mode][0], got["helpers"][0]) and np.array_equal(got[mode][1], got["helpers"][1]), mode
         for a, b in zip(got[mode][3], got["helpers"][3]):
             assert np.array_equal(a, b), mode
