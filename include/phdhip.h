@@ -246,6 +246,11 @@ const int32_t* phd_resample_sources(phd_navigator* nav, int* length, uint8_t* re
  *   phd_stage_map(stage, particle) reads one particle's mixture after that stage (phd_map's conventions):
  *       PHD_STAGE_PREDICTED  ≙ PredictConditional (PHDNavigator.cs:793-819): state map -> predicted (prior + births)
  *       PHD_STAGE_CORRECTED  ≙ CorrectConditional (:829-906) fused with the MinWeight cut of PruneModel, unsorted
+ *                            (the WHOLE list down to MinWeight. A step — phd_slam_update, phd_step_async, phd_step_local_async —
+ *                            may emit fewer entries than a stage run: PruneModel keeps only the MaxQuantity heaviest entries,
+ *                            so a step leaves out detection updates whose exact weight lies below a floor that MaxQuantity
+ *                            entries are certain to reach; the pruned maps and everything behind them are the same bits. A
+ *                            step's emitted list is never exposed: only a stage run's is, through this stage.)
  *       PHD_STAGE_PRUNED     ≙ PruneModel (:913-948)
  *   phd_stage_alpha()        ≙ WeightAlpha (:373-393), one value per particle
  *   phd_stage_setloglik()    ≙ SetLogLikelihood (:462-515), one value per particle                                        */

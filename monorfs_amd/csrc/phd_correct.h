@@ -44,7 +44,7 @@ __device__ __forceinline__ void load_predicted(const DevParams& prm, const StepB
 // which k_prune_merge does not see (it orders by weight and canonical index).
 #define EMIT_CAP 2048   // queue entries scanned per chunk (512 per wave); what is kept of them fits the two lists
 #define EMIT_RUN 4      // measurements a lane takes with one component (a longer run is cut: its wave would wait for it)
-#define EMIT_LDS_DOUBLES (EXPTAB_N + 5 * 256 + EMIT_CAP + 4)   // etab, ldenom[256], denom[256], z[256][3] | ints: list[EMIT_CAP], lead[EMIT_CAP], npair, nlist, nlead
+#define EMIT_LDS_DOUBLES (EXPTAB_N + 5 * 256 + EMIT_CAP + 4)   // etab, ldenom[256], denom[256], z[256][3] | ints: list[EMIT_CAP], lead[EMIT_CAP], npair, nlist, nlead, -, double floor
 // LEAN (the fused launch k_emit_prune, compiled at the prune's 128 registers): the component's mean and covariance are read AGAIN
 // behind the gain instead of living through the 3 x 3 inverse; where the registers are not short (k_emit_finish at three waves
 // per SIMD, the one-launch chain) the second read only adds a trip to the chain.
@@ -63,6 +63,7 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 	int& s_npair = lead[EMIT_CAP];
 	int& s_nlist = lead[EMIT_CAP + 1];
 	int& s_nlead = lead[EMIT_CAP + 2];
+	double& s_floor = *(double*) (lead + EMIT_CAP + 4);   // MinWeight, or the cut floor above it: what an entry's exact weight must reach to be emitted
 	const int p = a.p0 + blockIdx.x, tid = threadIdx.x;
 	const int M = a.M;
 	const MixView vin = bank_view(a, SEL_IN);
@@ -74,12 +75,20 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 	const int nc0 = a.cand_count[(size_t) p * 4], nc1 = a.cand_count[(size_t) p * 4 + 1], nc2 = a.cand_count[(size_t) p * 4 + 2],
 	          nc3 = a.cand_count[(size_t) p * 4 + 3];
 	const bool overflow = nc0 > segcap || nc1 > segcap || nc2 > segcap || nc3 > segcap;
-#ifdef PHD_STAMPS   // diagnostic build, PHD_STAMP_KERNEL=7: wave 0's cycles in the Kalman path, its rounds, the runs and the queue length
+#ifdef PHD_STAMPS   // diagnostic build, PHD_STAMP_KERNEL=7: wave 0's cycles in the Kalman path, its rounds, the runs and the queue length; the cut floor's stretch
 	const long long em_t0 = clock64();
-	long long em_pair = 0, em_nb = 0, em_runs = 0, em_setup = 0, em_scan = 0;
+	long long em_pair = 0, em_nb = 0, em_runs = 0, em_setup = 0, em_scan = 0, em_cut = 0;
 #endif
+	// (the cut floor below; workgroup-uniform. Nothing can be cut from a list of at most MaxQuantity entries — small maps, the
+	// reference's own scenes —, and a stage run keeps the whole list: neither pays for the pass)
+	const int ncut = prm.maxq;   // (the prune's own cut, min(MaxQuantity, its LDS capacity), is never larger: a larger K only lowers the floor)
+	const bool cutpass = !overflow && !a.emit_all && nmis + nc0 + nc1 + nc2 + nc3 > ncut;
+	int* const chist = list;     // [1024] the floor's histogram, where the lists of the scan go afterwards
+	if (cutpass) {
+		for (int t = tid; t < 1024; t += 256) chist[t] = 0;
+	}
 	exp_tab_init(etab, tid);
-	if (tid == 0) s_npair = 0;
+	if (tid == 0) { s_npair = 0; s_floor = prm.minw; }
 	const double* denom = a.denom + (size_t) p * a.Mcap;
 	for (int k = tid; k < M; k += 256) {
 		const double dk = denom[k];
@@ -87,10 +96,10 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 		sz[k * 3] = a.z[k * 3]; sz[k * 3 + 1] = a.z[k * 3 + 1]; sz[k * 3 + 2] = a.z[k * 3 + 2];
 	}
 	__syncthreads();   // every thread has read emit_count before thread 0 rewrites it
+	const int2*   cands = (const int2*) a.cand + (size_t) p * a.candcap;
 	PoseD pose = load_pose(bin.poses + (size_t) p * 7);   // (the same in every lane: scalar registers)
 	pose.t[0] = uniform_d(pose.t[0]); pose.t[1] = uniform_d(pose.t[1]); pose.t[2] = uniform_d(pose.t[2]);
 	pose.qw = uniform_d(pose.qw); pose.qx = uniform_d(pose.qx); pose.qy = uniform_d(pose.qy); pose.qz = uniform_d(pose.qz);
-	const int2*   cands = (const int2*) a.cand + (size_t) p * a.candcap;
 	// Component c and its run of measurements: list[start .. start + len) (kf >= 0: the one measurement kf instead — the
 	// fallback below). comp_measure (phd_device.h) written out in its own order of operations, so that what is dead can go early:
 	// the detection probability as soon as h(m) is known.
@@ -187,7 +196,7 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 			const double d2  = quad_gen(Sinv, n0, n1, n2);
 			const double qz  = qmult * exp_neg(-0.5 * d2, etab);   // mc.Evaluate(z)
 			const double wgt = pdw * qz / sden[k];                 // :899
-			if (wgt < prm.minw) continue;
+			if (wgt < s_floor) continue;   // MinWeight, or the cut floor above it (strict; a NaN stays)
 			const int slot = nmis + atomicAdd(&s_npair, 1);
 			if (slot >= a.ecap) continue;
 			double mn[3];
@@ -200,12 +209,81 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 		}
 	};
 	if (!overflow) {
+		// ---- The cut floor: a weight that MaxQuantity entries of the corrected list are certain to reach, found BEFORE the Kalman path.
+		// PruneModel keeps the first K = min(MaxQuantity, #w >= MinWeight) entries of the list sorted by weight (PHDNavigator.cs:913-948;
+		// prune_merge_body's `cut`) and never reads the rest, so a detection update that must rank behind K others need not be computed.
+		// Counted into the prune's own weight bins (phd_device.h): the misdetection copies' exact weights, which k_sweep has written,
+		// and for every queued pair a LOWER bound of its final weight — exponent x of the queue minus log(denominator), minus the margin
+		// the pre-filter of the scan trusts in the other direction (1e-3 + 1e-6 |x|) and 1e-3 more for the float32 exp (its error and that
+		// of its float32 argument, |x| <= 80, stay below 2e-5). The floor is the lower edge of the bin in which the count, from the top
+		// bin down, reaches K — MinWeight when that is bin 0.
+		// Why no bit of any result changes: every counted number is <= the true weight of a DISTINCT entry of the corrected list
+		// (the copies; each queued pair once), so at least K entries have a true weight >= floor and the true K-th largest weight is
+		// >= floor. An entry whose exact weight is STRICTLY below the floor therefore ranks strictly behind K entries — no tie rule
+		// (canonical index) brings it inside the cut — and every entry at or above the floor is still emitted, by the same arithmetic:
+		// the kept set, its order and everything behind the prune are the same bits. What decides is the exact weight in the
+		// reference's arithmetic (component_run); the approximate numbers only rule out, in the scan, what that test would drop anyway.
+		// The compare is strict and written so that a NaN (which the ABI does not let in) would be kept.
+		if (cutpass) {   // (workgroup-uniform)
+#ifdef PHD_STAMPS
+			const long long em_c0 = clock64();
+#endif
+			// (the particle's number through an empty asm, as in prune_merge_body: the compiler otherwise keeps this block's queue address
+			// for the scan, in a register pair it then spills)
+			int pc = p;
+			asm volatile("" : "+s"(pc));
+			const int wv = tid >> 6, lane = tid & 63;
+			const unsigned int bbase = weight_bin_base(prm.minw);
+			const double* mw = a.emit_w + (size_t) pc * a.ecap;
+			int e0 = tid;
+			asm volatile("" : "+v"(e0));   // (likewise: no address shared with the staging loop above)
+			for (int e = e0; e < nmis; e += 256) atomicAdd(&chist[weight_bin_of_bits((unsigned long long) __double_as_longlong(mw[e]), bbase)], 1);
+			const int ncw = (wv == 0) ? nc0 : ((wv == 1) ? nc1 : ((wv == 2) ? nc2 : nc3));
+			const int2* seg = (const int2*) a.cand + (size_t) pc * a.candcap + (size_t) wv * segcap;
+			for (int j = lane; j < ncw; j += 64) {
+				const int2 cd = seg[j];
+				const double x = (double) __int_as_float(cd.y);
+				const double lb = x - ldenom[cd.x & 255] - 2e-3 - 1e-6 * fabs(x);
+				const float wl = (lb == lb) ? __expf((float) ((lb < 80.0) ? lb : 80.0)) : 0.0f;
+				atomicAdd(&chist[weight_bin_of_bits((unsigned long long) __double_as_longlong((double) wl), bbase)], 1);
+			}
+			__syncthreads();
+			// every wave walks the bins from the top (lane l: bins 1023 - 16 l .. 1008 - 16 l), as the prune does: no barrier behind it;
+			// the scan's first barrier stands between these reads and the lists' first writes
+			int cq[16], mine = 0;
+#pragma unroll
+			for (int q = 0; q < 16; q++) { cq[q] = chist[1023 - (16 * lane + q)]; mine += cq[q]; }
+			int incl = mine;
+#pragma unroll
+			for (int o = 1; o < 64; o <<= 1) {
+				const int y = __shfl_up(incl, o, 64);
+				if (lane >= o) incl += y;
+			}
+			int run = incl - mine, tb = 0;
+#pragma unroll
+			for (int q = 0; q < 16; q++) {
+				if (run < ncut && ncut <= run + cq[q]) tb = 1023 - (16 * lane + q);
+				run += cq[q];
+			}
+#pragma unroll
+			for (int o = 32; o > 0; o >>= 1) tb = max(tb, __shfl_xor(tb, o, 64));
+			tb = __builtin_amdgcn_readfirstlane(tb);
+			// (the floor waits in LDS, for the scan and behind the Kalman path: a register pair kept that long was spilled. Every wave
+			// writes the same number and reads it back behind its own write)
+			if (tb > 0 && lane == 0) s_floor = fmax(weight_bin_edge(tb, bbase), prm.minw);
+			lds_fence();
+			__builtin_amdgcn_wave_barrier();
+#ifdef PHD_STAMPS
+			em_cut = clock64() - em_c0;
+#endif
+		}
 		// Most queued pairs fail once the real denominator is known. Their exponent x = log(PD w q) travels with them as a
 		// float32: x - log(denom) < log(MinWeight) by more than the float32 rounding settles it; the others go to the list.
+		// (with a cut floor: below log(floor) — what component_run's exact test against the floor would drop)
 		const int wv = tid >> 6, lane = tid & 63;
-		const double lminw = log(prm.minw);
+		const double lminw = log(s_floor);
 		const int ncw = (wv == 0) ? nc0 : ((wv == 1) ? nc1 : ((wv == 2) ? nc2 : nc3));
-		const int ncmax = max(max(nc0, nc1), max(nc2, nc3));
+		const int ncmax = __builtin_amdgcn_readfirstlane(max(max(nc0, nc1), max(nc2, nc3)));   // (a scalar: as a vector register it was spilled across the chunk loop)
 		const int2* seg = cands + (size_t) wv * segcap;
 		// (measured and dropped: a quarter of the lists per wave with scalar counters — no LDS atomic, no shuffle of the bases in
 		// the scan —: the scan 22.6 k -> 21.3 k cycles of the body's 80 k, 48 bytes of scratch instead of 12; eight groups of the
@@ -214,7 +292,7 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 		// loads, all eight in one trip, the product build: config B 0.608 -> 0.610 ms per step, S 3.45 -> 3.40. The scan is not
 		// waiting for the queue: its ~200 instructions per group issue at the pace the three other workgroups' Kalman paths leave.)
 #ifdef PHD_STAMPS
-		em_setup = clock64() - em_t0;
+		em_setup = clock64() - em_t0 - em_cut;
 #endif
 		for (int ch0 = 0; ch0 < ncmax; ch0 += EMIT_CAP / 4) {   // (workgroup-uniform; one trip unless a wave queued more than 512 pairs)
 #ifdef PHD_STAMPS
@@ -290,7 +368,7 @@ __device__ __forceinline__ void emit_finish_body(const DevParams& prm, const Ste
 		if (tid == 0 && a.stamps && a.stamp_kernel == 7) {
 			double* o = a.stamps + (size_t) p * 16;
 			o[0] = 0; o[1] = (double) (clock64() - em_t0); o[2] = (double) em_pair; o[3] = (double) em_nb; o[4] = (double) em_runs; o[5] = (double) (nc0 + nc1 + nc2 + nc3);
-			o[6] = (double) em_setup; o[7] = (double) em_scan;
+			o[6] = (double) em_setup; o[7] = (double) em_scan; o[8] = (double) em_cut; o[9] = (double) s_npair; o[10] = s_floor;
 		}
 #endif
 	}

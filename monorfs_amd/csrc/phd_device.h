@@ -504,6 +504,24 @@ __device__ __forceinline__ double uniform_d(double v)
 	return __hiloint2double(hi, lo);
 }
 
+// The weight bins of the MaxQuantity cut (the histogram of k_prune_merge, the cut floor of the emit body): exponent and five
+// mantissa bits of a positive double, counted from MinWeight's own bin up — 1024 bins, a relative width of 1 / 32 each; what lies
+// below bin 0 or above bin 1023 counts with them. `bits`: the double's bit pattern, or its prune_key (the top bit falls out).
+__device__ __forceinline__ unsigned int weight_bin_base(double minw)
+{
+	return (unsigned int) (((unsigned long long) __double_as_longlong(minw) << 1) >> 48);
+}
+__device__ __forceinline__ int weight_bin_of_bits(unsigned long long bits, unsigned int base)
+{
+	const unsigned int k = (unsigned int) ((bits << 1) >> 48);
+	return (int) min(max((int) k - (int) base, 0), 1023);
+}
+// the smallest double of bin b (1 <= b <= 1023; bin 0 has no lower edge)
+__device__ __forceinline__ double weight_bin_edge(int b, unsigned int base)
+{
+	return __longlong_as_double((long long) ((unsigned long long) (base + (unsigned int) b) << 47));
+}
+
 // s / d for 0 <= s < 2^24 and 1 <= d without the integer-division sequence (rd = 1.0f / d): a float quotient is off by at
 // most one
 __device__ __forceinline__ int small_div(int s, int d, float rd)

@@ -88,7 +88,7 @@ struct StepBufs {
 	const int* sel; // [SEL_STRIDE] device-resident roles of the banks for this step (no host round trip to rotate them)
 	const int* inslot;   // [P] slot of particle p's mixture in the INMIX bank
 	const double* z;         // [M][3]
-	// corrected-but-unpruned components (weight >= MinWeight), unsorted
+	// corrected-but-unpruned components (weight >= MinWeight; in a step: those at or above the cut floor, see emit_all), unsorted
 	double* emit_w;      // [P][ecap]
 	int*    emit_idx;    // [P][ecap] canonical position in the reference's `corrected` list
 	double* emit_rec;    // [P][ecap][10] the detection updates as component records (w, mean, covariance upper triangle); not written for the misdetection copies
@@ -129,6 +129,8 @@ struct StepBufs {
 	double* ratio;       // [P] the density part of log alpha, left by whichever of a particle's two workgroups in k_particle_chain has it (alpha_meet)
 	int     all_pairs;   // 1: k_sweep evaluates every (component, measurement) pair, the radius gate only masks (SURVEY §8d's benchmark
 	                     // mode: the unit count P C M is exact); 0: a visit whose 64 pairs all lie outside the gate is skipped
+	int     emit_all;    // 1 (phd_stage_run alone): the emit body writes every corrected component that reaches MinWeight; 0 (every step): it may leave
+	                     // out detection updates that cannot survive the MaxQuantity cut of the prune behind it (the cut floor, phd_correct.h)
 	int     stamp_kernel; // which kernel writes them (env PHD_STAMP_KERNEL): 2 prune, 3 assoc, 4 density, 1 correct, 5 the one-launch chain
 	// k_particle_chain with a HELPER workgroup per particle for the densities of WeightAlpha (two workgroups per particle for that body)
 	int           dsplit;   // 1: the launch has 2 P workgroups, the second P are the helpers (2 - 4: test and measuring switches, PHD_DSPLIT_LATE)

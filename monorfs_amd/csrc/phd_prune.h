@@ -268,11 +268,8 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 			int& s_fill = hist[1026];
 			int& s_maxb = hist[1027];
 			unsigned int* const out = (unsigned int*) (hist + 1032);   // [capN]
-			const unsigned int base = (unsigned int) (((unsigned long long) __double_as_longlong(prm.minw) << 1) >> 48);
-			auto bin_of_bits = [&](unsigned long long bits) {          // bits of a positive double, or its prune_key (the top bit falls out)
-				const unsigned int k = (unsigned int) ((bits << 1) >> 48);
-				return (int) min(max((int) k - (int) base, 0), 1023);
-			};
+			const unsigned int base = weight_bin_base(prm.minw);
+			auto bin_of_bits = [&](unsigned long long bits) { return weight_bin_of_bits(bits, base); };   // (phd_device.h: the emit body's cut floor counts into the same bins)
 			auto bin_of = [&](double w) { return bin_of_bits((unsigned long long) __double_as_longlong(w)); };
 			for (int t = tid; t < 1028; t += 256) hist[t] = 0;
 			__syncthreads();

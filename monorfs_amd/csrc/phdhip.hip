@@ -294,7 +294,7 @@ StepBufs make_bufs(phd_navigator* nav)
 	b.cand_count = nav->d_cand_count; b.denom = nav->d_denom;
 	b.cand = nav->d_cand; b.candcap = nav->candcap;
 	b.dsplit = 0; b.dstamp = 0; b.dsync = nav->d_dsync;
-	b.alm = nav->d_alm; b.aJ = nav->d_aJ; b.account = nav->d_account; b.srec = nav->d_srec; b.outw = nav->d_outw; b.wcopy = nav->d_wcopy; b.cover = nav->d_cover; b.stamps = nav->d_stamps; b.ratio = nav->d_ratio; b.all_pairs = nav->all_pairs ? 1 : 0; b.stamp_kernel = getenv("PHD_STAMP_KERNEL") ? atoi(getenv("PHD_STAMP_KERNEL")) : 2;
+	b.alm = nav->d_alm; b.aJ = nav->d_aJ; b.account = nav->d_account; b.srec = nav->d_srec; b.outw = nav->d_outw; b.wcopy = nav->d_wcopy; b.cover = nav->d_cover; b.stamps = nav->d_stamps; b.ratio = nav->d_ratio; b.all_pairs = nav->all_pairs ? 1 : 0; b.emit_all = 0; b.stamp_kernel = getenv("PHD_STAMP_KERNEL") ? atoi(getenv("PHD_STAMP_KERNEL")) : 2;
 	return b;
 }
 
@@ -1578,6 +1578,7 @@ int phd_stage_run(phd_navigator* nav, const double* z3, int nmeasurements, uint8
 	rc = sync_state(nav);
 	if (rc) return rc;
 	StepBufs b = make_bufs(nav);
+	b.emit_all = 1;   // PHD_STAGE_CORRECTED is the whole list down to MinWeight: no cut floor (phd_correct.h)
 	HC(hipMemsetAsync(nav->d_bigws_used, 0, 8, nav->stream));
 	rc = launch_map(nav, b, with_alpha != 0);
 	if (rc) return rc;

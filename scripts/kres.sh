@@ -8,6 +8,10 @@ MODE=${1:-all}; shift || true
 T=$(mktemp -d)
 if [ "$MODE" = ep ]; then
   printf '#define PHD_ONLY_EP\n#include "%s/monorfs_amd/csrc/phd_kernels.h"\n' "$PWD" > $T/ep.hip
+  # (the emit kernels are templates over the depth map: instantiated here, as the variant table of phdhip.hip does)
+  for d in false true; do
+    printf 'template __global__ void k_emit_finish<%s>(const DevParams, const StepBufs);\ntemplate __global__ void k_emit_prune<%s>(const DevParams, const StepBufs, int);\n' $d $d >> $T/ep.hip
+  done
   SRC=$T/ep.hip
 else
   SRC=monorfs_amd/csrc/phdhip.hip
