@@ -150,9 +150,13 @@ def set_log_likelihood_bruteforce(p, pose7, lm, z, quasi=False):
     return mx + np.log(np.sum(np.exp(vals - mx)))
 
 
-def random_case(rng, p, J, M):
-    """landmarks inside the field of view of a random pose, measurements near some of them + clutter"""
-    pose = np.concatenate([rng.normal(0, 0.05, 3), [1.0, 0.0, 0.0, 0.0] + rng.normal(0, 0.03, 4)])
+def random_case(rng, p, J, M, pose=None):
+    """landmarks inside the field of view of a random pose, measurements near some of them + clutter. pose: a quaternion
+    (w, x, y, z), taken as it is, at a location up to 2 m off the origin along every axis; None: next to the identity."""
+    if pose is None:
+        pose = np.concatenate([rng.normal(0, 0.05, 3), [1.0, 0.0, 0.0, 0.0] + rng.normal(0, 0.03, 4)])
+    else:
+        pose = np.concatenate([rng.uniform(-2, 2, 3), np.asarray(pose, float)])
     zs = np.column_stack([rng.uniform(-250, 250, J), rng.uniform(-180, 180, J), rng.uniform(0.4, 1.7, J)])
     lm = np.array([measure_to_map(p, pose, zz) for zz in zs])
     z = []
