@@ -724,13 +724,6 @@ __host__ __device__ inline AlphaLds alpha_lds(int MP, int ncap)
 	return l;
 }
 
-// per-particle HBM slab used instead of LDS when J > ALPHA_JL (doubles; ints packed two per double)
-__host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap)
-{
-	// lm 3J, dw J, zh 3J, lpd J, res J, adj 4J, part 4J  |  pick, dsrc, labl, roots : 4J ints  |  lmd J, memL J, memZ J, cnt J ints
-	return (size_t) 23 * Jcap;
-}
-
 // QUASI = false: BestMapEstimate + SetLogLikelihood of particle p (k_alpha_assoc).
 // QUASI = true : QuasiSetLogLikelihood (PHDNavigator.cs:526-713, value) of candidate pose p against one
 //                given landmark set — the same association sum with everything fully visible: constant PD (:574-575),
@@ -750,10 +743,41 @@ __host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap)
 #ifndef DENS_JL
 #define DENS_JL 128   // landmarks whose partial sums stay in LDS
 #endif
+// Per-particle HBM slab (a.jscratch; ints packed two per double). Three users, never live together:
+//   the association body when J > ALPHA_JL: lm 3J, dw J, zh 3J, lpd J, res J, adj 4J | pick, dsrc, labl, roots: 4J ints | lmd, memL, memZ J, cnt J ints
+//   the gradient first pass (J <= ALPHA_JL, the arrays above are in LDS then): cluster headers | jpall | elist
+//   the density sums when J > DENS_JL (the association's arrays are dead by then): partc, partp, 4J each
+struct AlphaSlab {
+	// in units of Jcap doubles
+	static constexpr int lm = 0, dw = 3, zh = 4, lpd = 7, res = 8, adj = 9, ints = 17, lmd = 19, memL = 20, memZ = 21, cnt = 22, total = 23;
+	static constexpr int partc = 0, partp = 13;
+	// in units of Jcap ints, from `ints`
+	static constexpr int i_pick = 0, i_dsrc = 1, i_labl = 2, i_roots = 3;
+	// in doubles: headers and jpall are sized for ALPHA_JL landmarks, elist takes what the slab has left. At a small Jcap that is
+	// nothing (ecap <= 0, known only at run time): the first pass then leaves every cluster to the ordered replay
+	static constexpr int g_hdr = 0, g_jpall = g_hdr + QGRAD_HDR * ALPHA_JL, g_elist = g_jpall + 18 * ALPHA_JL;
+};
+static_assert(AlphaSlab::lm + 3 <= AlphaSlab::dw && AlphaSlab::dw + 1 <= AlphaSlab::zh && AlphaSlab::zh + 3 <= AlphaSlab::lpd &&
+              AlphaSlab::lpd + 1 <= AlphaSlab::res && AlphaSlab::res + 1 <= AlphaSlab::adj && AlphaSlab::adj + 4 <= AlphaSlab::ints &&
+              AlphaSlab::ints + (AlphaSlab::i_roots + 2) / 2 <= AlphaSlab::lmd && AlphaSlab::lmd + 1 <= AlphaSlab::memL &&
+              AlphaSlab::memL + 1 <= AlphaSlab::memZ && AlphaSlab::memZ + 1 <= AlphaSlab::cnt && AlphaSlab::cnt + 1 <= AlphaSlab::total &&
+              AlphaSlab::partc + 4 <= AlphaSlab::partp && AlphaSlab::partp + 4 <= AlphaSlab::total,
+              "AlphaSlab: the Jcap-scaled arrays that are live together overlap, or pass the total");
+__host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap) { return (size_t) AlphaSlab::total * Jcap; }
 // `helper_go` (k_particle_chain with a helper workgroup per particle, a.dsplit): where the map estimate is final the body
 // publishes it and — if the particle's helper has reported, from the same XCD — hands the density sums (alpha_density_body) to it,
 // which then run BESIDE the association below instead of behind it; *helper_go says whether it did.
 __device__ __forceinline__ unsigned int my_xcd() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u; }   // HW_REG_XCC_ID
+
+// does landmark j hold a detection entry: adj[j][MW] has a bit for every measurement inside its gate
+template <int MW>
+__device__ __forceinline__ bool has_detection(const unsigned long long* adj, int j)
+{
+	bool has = false;
+#pragma unroll
+	for (int b = 0; b < MW; b++) has |= adj[(size_t) j * MW + b] != 0;
+	return has;
+}
 
 template <int ZB, bool QUASI, bool GRAD = false, int TAG = 0, bool DEPTH = false>
 __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const StepBufs& a, int ncap, double* smem, double* gws = nullptr,
@@ -957,21 +981,21 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 	const bool inlds = J <= JL;
 	const int  JS = inlds ? JL : a.Jcap;               // stride of the landmark-indexed arrays
 	double* gj = a.jscratch + (size_t) p * alpha_jscratch_doubles(a.Jcap);
-	double* lm   = inlds ? smem + lay.lm     : gj;                       // [3][JS] landmark means of the map estimate
-	double* dw   = inlds ? smem + lay.p1_dw  : gj + 3 * (size_t) JS;     // [JS] derived (w - 1) entries, FIFO
-	double* zh   = inlds ? smem + lay.p3_zh  : gj + 4 * (size_t) JS;     // [3][JS] h(m_j)
-	double* lpd  = inlds ? smem + lay.p3_pdj : gj + 7 * (size_t) JS;     // [JS] log PD of landmark j
-	double* lmd  = inlds ? smem + lay.p3_lmd : gj + 19 * (size_t) JS;    // [JS] log(1 - PD)
-	double* res  = inlds ? smem + lay.p3_res : gj + 8 * (size_t) JS;     // [JS] per-cluster log-sum-exp, in cluster order
-	unsigned long long* adj = (unsigned long long*) (inlds ? smem + lay.p3_adj : gj + 9 * (size_t) JS);   // [JS][MW]
-	int* gi      = (int*) (gj + 17 * (size_t) JS);
-	int* pick    = inlds ? (int*) (smem + lay.pick) : gi;                // [JS] component picked for landmark j
-	int* dsrc    = inlds ? sortsrc + lay.ns : gi + JS;                   // [JS]
-	int* labl    = inlds ? (int*) (smem + lay.p3_int) : gi + 2 * JS;     // [JS]
-	int* roots   = inlds ? labl + JL : gi + 3 * JS;                      // [JS]
-	int* cnt     = inlds ? labl + 2 * JL : (int*) (gj + 22 * (size_t) JS);   // [JS] members of the cluster rooted at j: landmarks | measurements << 16
-	unsigned long long* memL = (unsigned long long*) (inlds ? smem + lay.p3_mem : gj + 20 * (size_t) JS);        // [JS] its first 5 landmarks, 12-bit fields
-	unsigned long long* memZ = (unsigned long long*) (inlds ? smem + lay.p3_mem + JL : gj + 21 * (size_t) JS);   // [JS] its first 5 measurements
+	double* lm   = inlds ? smem + lay.lm     : gj + AlphaSlab::lm * (size_t) JS;   // [3][JS] landmark means of the map estimate
+	double* dw   = inlds ? smem + lay.p1_dw  : gj + AlphaSlab::dw * (size_t) JS;   // [JS] derived (w - 1) entries, FIFO
+	double* zh   = inlds ? smem + lay.p3_zh  : gj + AlphaSlab::zh * (size_t) JS;   // [3][JS] h(m_j)
+	double* lpd  = inlds ? smem + lay.p3_pdj : gj + AlphaSlab::lpd * (size_t) JS;   // [JS] log PD of landmark j
+	double* lmd  = inlds ? smem + lay.p3_lmd : gj + AlphaSlab::lmd * (size_t) JS;   // [JS] log(1 - PD)
+	double* res  = inlds ? smem + lay.p3_res : gj + AlphaSlab::res * (size_t) JS;   // [JS] per-cluster log-sum-exp, in cluster order
+	unsigned long long* adj = (unsigned long long*) (inlds ? smem + lay.p3_adj : gj + AlphaSlab::adj * (size_t) JS);   // [JS][MW]
+	int* gi      = (int*) (gj + AlphaSlab::ints * (size_t) JS);
+	int* pick    = inlds ? (int*) (smem + lay.pick) : gi + AlphaSlab::i_pick * JS;   // [JS] component picked for landmark j
+	int* dsrc    = inlds ? sortsrc + lay.ns : gi + AlphaSlab::i_dsrc * JS;   // [JS]
+	int* labl    = inlds ? (int*) (smem + lay.p3_int) : gi + AlphaSlab::i_labl * JS;   // [JS]
+	int* roots   = inlds ? labl + JL : gi + AlphaSlab::i_roots * JS;   // [JS]
+	int* cnt     = inlds ? labl + 2 * JL : (int*) (gj + AlphaSlab::cnt * (size_t) JS);   // [JS] members of the cluster rooted at j: landmarks | measurements << 16
+	unsigned long long* memL = (unsigned long long*) (inlds ? smem + lay.p3_mem : gj + AlphaSlab::memL * (size_t) JS);   // [JS] its first 5 landmarks, 12-bit fields
+	unsigned long long* memZ = (unsigned long long*) (inlds ? smem + lay.p3_mem + JL : gj + AlphaSlab::memZ * (size_t) JS);   // [JS] its first 5 measurements
 	int* labz    = (int*) (smem + lay.p3_int) + 3 * JL;                  // [MP]
 	double* xreg = smem + lay.p3_x;                                      // mats [25][4]  |  Murty scratch
 	// When the largest weight minus one does not exceed the J-th largest weight no appended entry can be
@@ -1156,9 +1180,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 				const int j = j0 + lane;
 				bool isroot = false;
 				if (j < J) {
-					bool has = false;
-#pragma unroll
-					for (int b = 0; b < MW; b++) has |= adj[(size_t) j * MW + b] != 0;
+					const bool has = has_detection<MW>(adj, j);
 					isroot = has && labl[j] == j;
 				}
 				unsigned long long bal = ballot64(isroot);
@@ -1319,9 +1341,9 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 			int* const gZ = gL + 8;
 			// the particle's scratch: cluster headers | MeasurementJacobianP of every landmark (:591), computed here by all
 			// threads at once rather than by the one or two lanes a cluster has landmarks for | the clusters' weight lists
-			double* const jpall = gj + (size_t) QGRAD_HDR * JL;
-			double* const elist = jpall + (size_t) 18 * JL;
-			const int ecap = (int) alpha_jscratch_doubles(a.Jcap) - (QGRAD_HDR + 18) * JL;
+			double* const jpall = gj + AlphaSlab::g_jpall;
+			double* const elist = gj + AlphaSlab::g_elist;
+			const int ecap = (int) alpha_jscratch_doubles(a.Jcap) - AlphaSlab::g_elist;
 			const int gt = (lane < 6) ? lane : 0;
 			if (tid == 0) s_ebump = 0;
 			if (ecap > 0) {
@@ -1841,7 +1863,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 					};
 					while (ri <= lastbig) {
 						const int ns = s_g2lds ? light_run(s_g2, s_g2 + QGRAD_G2_CLUSTERS * QGRAD_HDR, ri)
-						                       : light_run(gj, gj + (size_t) (QGRAD_HDR + 18) * JL, ri);
+						                       : light_run(gj + AlphaSlab::g_hdr, gj + AlphaSlab::g_elist, ri);
 						ri += ns;
 						if (ri <= lastbig && ns < SEG) {
 #pragma unroll
@@ -1945,9 +1967,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		double tpart = 0;
 		for (int r = tid; r < nroots; r += 256) tpart += res[r];
 		for (int j = tid; j < J; j += 256) {
-			bool has = false;
-#pragma unroll
-			for (int b = 0; b < MW; b++) has |= adj[(size_t) j * MW + b] != 0;
+			const bool has = has_detection<MW>(adj, j);
 			if (!has) tpart += lmd[j];
 		}
 		for (int k = tid; k < M; k += 256) {
@@ -2086,8 +2106,8 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 	const int JS = a.Jcap;
 	const double* lm = a.alm + (size_t) p * 3 * JS;   // [3][Jcap]
 	double* gj = a.jscratch + (size_t) p * alpha_jscratch_doubles(a.Jcap);
-	double* partp = (J <= JL) ? partpl : gj + 13 * (size_t) JS;   // (the association kernel's arrays in the slab are dead by now)
-	double* partc = (J <= JL) ? partcl : gj;
+	double* partp = (J <= JL) ? partpl : gj + AlphaSlab::partp * (size_t) JS;   // (the association kernel's arrays in the slab are dead by now)
+	double* partc = (J <= JL) ? partcl : gj + AlphaSlab::partc * (size_t) JS;
 	const double* wcopy = a.wcopy + (size_t) p * (cap + a.Mcap);
 	const int* cover = a.cover + sbo;
 	if (!pre) exp_tab_init(etab, tid);

@@ -75,7 +75,14 @@ CASES = [
     # MinWeight 0: every gated pair is a candidate, the candidate queue of k_sweep overflows and the
     # all-pairs fallback runs; nothing is cut before the merge
     (2, 30, 24, 19, "steady", {"min_weight": 0.0, "emit_capacity": 4096}),
+    # a map estimate of one to four landmarks that hold detections: the literal enumeration of the association (TINY_MAPS)
+    (3, 4, 3, 20, "steady", {}),
+    (3, 3, 2, 21, "steady", {}),
+    (3, 5, 4, 22, "steady", {}),
 ]
+# the cases whose map estimate must have 1 <= J <= 4 landmarks, one of them detected, for every particle
+TINY_MAPS = [(3, 4, 3, 20, "steady", {}), (3, 3, 2, 21, "steady", {}), (3, 5, 4, 22, "steady", {})]
+assert all(c in CASES for c in TINY_MAPS)
 
 
 @pytest.mark.parametrize("P,C,M,seed,profile,over", CASES)
@@ -84,7 +91,7 @@ def test_stage_parity(nav_mod, P, C, M, seed, profile, over):
 
 
 @pytest.mark.parametrize("chain_max", [None, 0])
-@pytest.mark.parametrize("P,C,M,seed,profile,over", [CASES[1], (6, 130, 32, 12, "steady", {}), CASES[2], CASES[3], CASES[4], CASES[8]])
+@pytest.mark.parametrize("P,C,M,seed,profile,over", [CASES[1], (6, 130, 32, 12, "steady", {}), CASES[2], CASES[3], CASES[4], CASES[8], CASES[9]])
 def test_stage_parity_in_the_timed_mode(nav_mod, monkeypatch, chain_max, P, C, M, seed, profile, over):
     """the same stages against the oracle with phd_set_all_pairs(1) + phd_set_frozen(1) — the mode bench.py times —, through
     the one-launch chain (the default at these sizes) and through the separate kernels on two streams (PHD_CHAIN_MAX=0)"""
@@ -95,6 +102,10 @@ def test_stage_parity_in_the_timed_mode(nav_mod, monkeypatch, chain_max, P, C, M
 
 
 def stage_parity(nav_mod, P, C, M, seed, profile, over, timed_mode=False):
+    """every stage of one step against the oracle, particle by particle. The TINY_MAPS cases are there for one branch of the
+    association — fewer than five landmarks, with detections —, so their precondition is asserted: the oracle's BestMapEstimate
+    of every particle's pruned map has 1 <= J <= 4 landmarks, and a cluster of its association graph has more than one row (a
+    landmark with a measurement inside its gate)"""
     f = Frame(P, C, M, seed, weight_profile=profile) if C > 0 else Frame(P, 1, M, seed, weight_profile="survey")
     if C == 0:
         f.counts[:] = 0
@@ -114,6 +125,10 @@ def stage_parity(nav_mod, P, C, M, seed, profile, over, timed_mode=False):
         match_unordered(nav.CorrectConditional(i), tuple(x[keep] for x in cor), 1e-9)
         pr = orc.prune(p, cor)
         assert_mix_close(nav.PruneModel(i), pr, 1e-7, "prune[%d]" % i)
+        if (P, C, M, seed, profile, over) in TINY_MAPS:
+            lm = orc.best_map_estimate(pr)[0]
+            assert 1 <= len(lm) <= 4, "particle %d: the map estimate has %d landmarks, the case is built for 1 to 4" % (i, len(lm))
+            assert orc.set_log_likelihood(p, f.poses[i], lm, f.z)[2] >= 2, "particle %d: no landmark holds a detection" % i
         a, sll = orc.weight_alpha(p, f.poses[i], f.z, pred, pr)
         assert np.isclose(setll[i], sll, rtol=1e-9, atol=1e-9), "set log-likelihood[%d]: %r vs %r" % (i, setll[i], sll)
         assert np.isclose(alpha[i], a, rtol=1e-6, atol=0), "alpha[%d]: %r vs %r" % (i, alpha[i], a)
