@@ -2038,6 +2038,9 @@ __global__ __launch_bounds__(256, 4) void k_quasi_setll(const DevParams prm, con
 #ifndef PHD_DENS_WAVES
 #define PHD_DENS_WAVES 4
 #endif
+#ifndef PHD_DENS_PAIR
+#define PHD_DENS_PAIR 1   // two landmarks per lane for map estimates of at most DENS_JL landmarks (0: a landmark per lane, two components per trip)
+#endif
 #define DENS_LDS_DOUBLES (DENS_TILE * DENS_REC + 2 * (DENS_JL / 64) * 256 + EXPTAB_N + 2)
 // WeightAlpha's last line for a particle whose density sums and set log-likelihood come from two workgroups (k_particle_chain's helper
 // and main): each leaves its number (a.ratio / a.setll), waits until that store is in the L2 both sit behind and swaps the launch's
@@ -2123,12 +2126,84 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 	// over the predicted mixture adds ratio_c * (w_c N_c(m_j)) to the corrected sum as well, ratio_c = wcopy[c] / w_c
 	// (k_prune_merge, which also checks that the copy's moments are the component's up to Merge's rounding). The second
 	// sweep takes only the other corrected components (updated by a measurement, merged).
+	//
+	// Map estimates of at most JL landmarks (two blocks) — PHD_DENS_PAIR —: a lane holds TWO landmarks of a block. A block of S
+	// slots (64, or the power of two the remainder rounds up to) is LJ = S / 2 lanes with the landmarks jl and LJ + jl on lane jl,
+	// and the 64 / LJ lane groups of a wave take different components: the same (component, landmark) evaluations per trip as two
+	// components for one landmark each, for ONE record read per lane. The sums of both blocks stay in registers over a whole
+	// sweep (the tile loop outermost: records are staged once) and go to partp / partc once per sweep, neighbouring lane groups
+	// first exchanging the landmark slot they do not keep — lane l then holds slot l & (S - 1) of its wave's components, the
+	// layout the reduction below has always read. Which loop runs depends on J alone, so every workgroup that runs this body
+	// for a particle (k_alpha_density, the chain's main and helper workgroups) adds in the same order.
 	double plog_part = 0, clog_part = 0, pcount_part = pre ? pre_pcount : 0.0;
 	{
 		const int JB = (J + 63) >> 6;
+		const bool pair = PHD_DENS_PAIR && J > 0 && J <= JL;
 		// (the sum of the prior weights, sum w_pred: added up where the records are staged below — thread tid takes the
 		// components tid, tid + 256, ... there, in this order)
-		for (int i = tid; i < JB * 256; i += 256) { partp[i] = 0; partc[i] = 0; }
+		if (!pair) {
+			for (int i = tid; i < JB * 256; i += 256) { partp[i] = 0; partc[i] = 0; }
+		}
+		// the pair layout of block b: lane group width, first component and stride of this lane, its two landmarks
+		int  plj[2] = {1, 1}, pcc[2] = {0, 0}, pstep[2] = {256, 256};
+		unsigned int pj[2][2] = {};                 // [block][landmark slot]: the landmark's byte offset in a row of lm (a slot beyond
+		                                            // the block's landmarks: its first — a sum nobody reads)
+		bool ptwo[2] = {false, false};
+		double pacc[2][2] = {}, pcacc[2][2] = {};   // [block][landmark slot]: the sweep's sum; the corrected density's sum (both sweeps)
+		if (pair) {
+#pragma unroll
+			for (int b = 0; b < 2; b++) {
+				const int rem = min(64, J - b * 64);
+				if (rem <= 0) continue;
+				const int S = (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1))));
+				ptwo[b] = S > 1;
+				const int lj = ptwo[b] ? (S >> 1) : 1, G = 64 / lj, jl = lane & (lj - 1);
+				plj[b] = lj;
+				pcc[b] = wv * G + lane / lj;
+				pstep[b] = 4 * G;
+				pj[b][0] = 8u * (b * 64 + ((jl < rem) ? jl : 0));
+				pj[b][1] = 8u * (b * 64 + ((lj + jl < rem) ? lj + jl : 0));
+			}
+		}
+		// one block's share of a staged tile: every component of this lane's group at the lane's landmarks (their coordinates
+		// are read here, per tile, so that they do not live through the staging: twelve doubles from the cache)
+		auto pair_block = [&](const int b, const bool first, const int cend) {
+			double xa[3], xb[3];
+			unsigned int oa = pj[b][0], ob = pj[b][1];
+			asm volatile("" : "+v"(oa), "+v"(ob));   // (or six addresses per block are worked out ahead of the tile loop and spilled)
+#pragma unroll
+			for (int t = 0; t < 3; t++) {
+				const char* const row = (const char*) (lm + t * JS);   // (a uniform base and a 32-bit byte offset per lane)
+				xa[t] = *(const double*) (row + oa);
+				xb[t] = *(const double*) (row + ob);
+			}
+			auto visit = [&](const int cc, const bool two) {
+				const double* tt = tile + cc * DENS_REC;
+				double g[DENS_REC - 1];   // the record, read once for both landmarks (the weight ratio: first sweep only)
+#pragma unroll
+				for (int t = 0; t < DENS_REC - 1; t++) g[t] = (t < 10 || first) ? tt[t] : 0;
+				const double e1 = exp_pair(gauss_logw(g, xa[0] - g[0], xa[1] - g[1], xa[2] - g[2]), etab);
+				const double e2 = two ? exp_pair(gauss_logw(g, xb[0] - g[0], xb[1] - g[1], xb[2] - g[2]), etab) : 0.0;
+				if (first) {
+					pacc[b][0] += e1;
+					pcacc[b][0] = fma(g[10], e1, pcacc[b][0]);
+					if (two) {
+						pacc[b][1] += e2;
+						pcacc[b][1] = fma(g[10], e2, pcacc[b][1]);
+					}
+				}
+				else {
+					pcacc[b][0] += e1;
+					if (two) pcacc[b][1] += e2;
+				}
+			};
+			if (ptwo[b]) {
+				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) visit(cc, true);
+			}
+			else {   // (a block of one landmark: one per lane, 64 lane groups)
+				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) visit(cc, false);
+			}
+		};
 		for (int src = 0; src < 2; src++) {
 			const int total = (src == 0) ? np : no;
 			for (int c0 = 0; c0 < total; c0 += DENS_TILE) {
@@ -2175,7 +2250,17 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 					}
 				}
 				__syncthreads();
-				for (int jb = 0; jb < JB && cend > 0; jb++) {
+				if (pair) {
+					if (src == 0) {
+						pair_block(0, true, cend);
+						if (JB > 1) pair_block(1, true, cend);
+					}
+					else {
+						pair_block(0, false, cend);
+						if (JB > 1) pair_block(1, false, cend);
+					}
+				}
+				for (int jb = 0; jb < JB && cend > 0 && !pair; jb++) {
 					const int rem = min(64, J - jb * 64);
 					const int LJ  = (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1))));
 					const int G   = 64 / LJ, g = lane / LJ, jl = lane & (LJ - 1);
@@ -2216,6 +2301,23 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 					}
 				}
 				__syncthreads();
+			}
+			if (pair) {
+				// the sweep's sums, once: neighbouring lane groups hold the same two landmarks for different components — the even
+				// group keeps slot 0 and takes the odd group's, the odd group keeps slot 1 (own + the neighbour's)
+				double* const part = (src == 0) ? partp : partc;
+#pragma unroll
+				for (int b = 0; b < 2; b++) {
+					if (b >= JB) continue;
+					const double v0 = (src == 0) ? pacc[b][0] : pcacc[b][0], v1 = (src == 0) ? pacc[b][1] : pcacc[b][1];
+					double keep = v0;
+					if (ptwo[b]) {
+						const bool odd = (lane & plj[b]) != 0;
+						keep = odd ? v1 : v0;
+						keep += __shfl_xor(odd ? v0 : v1, plj[b], 64);
+					}
+					part[(b * 4 + wv) * 64 + lane] = keep;
+				}
 			}
 			__threadfence_block();
 			__syncthreads();

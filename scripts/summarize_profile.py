@@ -47,15 +47,15 @@ def main():
                                                         "sgpr": int(row["SGPR_Count"]), "lds": int(row["LDS_Block_Size"]),
                                                         "wg": int(row["Workgroup_Size_X"]), "grid": int(row["Grid_Size_X"])})
     pmc = {}
-    for sub in ("pmc_sq", "pmc_fetch", "pmc_write"):
+    for sub in ("pmc_lds", "pmc_sq", "pmc_fetch", "pmc_write"):   # (a counter in two passes: the later pass counts)
         for k, cs in load_counters(os.path.join(src, sub)).items():
             for c, vals in cs.items():
                 pmc.setdefault(k, {})[c] = sum(vals) / len(vals)
     out = {"source": src, "kernels": {}}
     lines = ["# %s" % name, "", "rocprofv3 --kernel-trace --stats + separate --pmc passes (scripts/profile_gpu.sh); values are per launch.",
              "HBM bytes = 2 x FETCH_SIZE x 1024 (gfx950 reports half of a wide streaming read) + WRITE_SIZE x 1024.", "",
-             "| kernel | calls | avg us | % | VGPR | LDS B | grid x wg | HBM read MB | HBM write MB | VALU insts/wave | VALU busy frac | wait-any frac | L2 hit |",
-             "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+             "| kernel | calls | avg us | % | VGPR | LDS B | grid x wg | HBM read MB | HBM write MB | VALU insts/wave | VALU busy frac | wait-any frac | L2 hit | LDS insts/wave | LDS bank-conflict / active cycles |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for k, st in sorted(stats.items(), key=lambda kv: -kv[1]["pct"]):
         if not k.startswith("k_"):
             continue
@@ -69,12 +69,14 @@ def main():
         busy = c.get("SQ_ACTIVE_INST_VALU", 0) / wc if wc else None
         wait = c.get("SQ_WAIT_ANY", 0) / wc if wc else None
         hit = c.get("TCC_HIT_sum", 0) / max(c.get("TCC_HIT_sum", 0) + c.get("TCC_MISS_sum", 0), 1) if "TCC_HIT_sum" in c else None
+        lds_per_wave = c.get("SQ_INSTS_LDS", 0) / waves if waves and "SQ_INSTS_LDS" in c else None
+        conflict = c.get("SQ_LDS_BANK_CONFLICT", 0) / c["SQ_LDS_IDX_ACTIVE"] if c.get("SQ_LDS_IDX_ACTIVE") else None
         out["kernels"][k] = {"trace": st, "resources": r, "pmc": c, "hbm_read_bytes": None if rd is None else rd * 1e6,
                              "hbm_write_bytes": None if wr is None else wr * 1e6}
         f = lambda v, fmt="%.2f": "-" if v is None else fmt % v
-        lines.append("| %s | %d | %.1f | %.1f | %s | %s | %sx%s | %s | %s | %s | %s | %s | %s |" % (
+        lines.append("| %s | %d | %.1f | %.1f | %s | %s | %sx%s | %s | %s | %s | %s | %s | %s | %s | %s |" % (
             k, st["calls"], st["avg_us"], st["pct"], r.get("vgpr", "-"), r.get("lds", "-"), r.get("grid", "-"), r.get("wg", "-"),
-            f(rd), f(wr), f(valu_per_wave, "%.0f"), f(busy), f(wait), f(hit)))
+            f(rd), f(wr), f(valu_per_wave, "%.0f"), f(busy), f(wait), f(hit), f(lds_per_wave, "%.0f"), f(conflict, "%.3f")))
     os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
     open(os.path.join(root, "profiles", name + ".md"), "w").write("\n".join(lines) + "\n")
     json.dump(out, open(os.path.join(root, "profiles", name + ".json"), "w"), indent=1)
