@@ -55,6 +55,9 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static IntPtr phd_poses(HandleRef nav, out int length);
 	[DllImport(Lib)] public extern static int    phd_map(HandleRef nav, int particle, out int ncomp, out IntPtr w, out IntPtr mean3, out IntPtr cov9);
 	[DllImport(Lib)] public extern static IntPtr phd_resample_sources(HandleRef nav, out int length, [MarshalAs(UnmanagedType.U1)] out bool resampled);
+	[DllImport(Lib)] public extern static int    phd_history_enable(HandleRef nav, int capacity);
+	[DllImport(Lib)] public extern static int    phd_history_append(HandleRef nav, double time);
+	[DllImport(Lib)] public extern static int    phd_trajectories(HandleRef nav, int[] particles, int nparticles, out int length, out IntPtr times, out IntPtr poses7, out IntPtr slots);
 }
 
 /// <summary>
@@ -182,7 +185,38 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 		fixed (double* pr = reading) fixed (double* pn = noise) {
 			Check(PhdHipLib.phd_update_motion(nav, (IntPtr) pr, OnlyMapping ? IntPtr.Zero : (IntPtr) pn, n, SimulatedVehicle<MeasurerT, Pose3D, PixelRangeMeasurement>.PerfectStill));
 		}
+		// the managed particles' WayPoints are not touched on this path: the device keeps the paths (EnableDeviceHistory)
+		if (DeviceHistory) { Check(PhdHipLib.phd_history_append(nav, time.TotalGameTime.TotalSeconds)); }
 		UpdateTrajectory(time);
+	}
+
+	/// <summary>True while the device keeps the particles' paths (EnableDeviceHistory).</summary>
+	public bool DeviceHistory { get; private set; }
+
+	/// <summary>The trajectory log on the device (phd_history_enable): room for `capacity` frames, 0 switches it off. Every call
+	/// restarts it at length 0, as does every reset (ResetHistory). Single-device handles only.</summary>
+	public void EnableDeviceHistory(int capacity)
+	{
+		Check(PhdHipLib.phd_history_enable(nav, capacity));
+		DeviceHistory = capacity > 0;
+	}
+
+	/// <summary>≙ VehicleParticles[particle].WayPoints (Vehicle.cs:141) as the device kept it: the path of that particle of the
+	/// current state through every resampling, oldest entry first (phd_trajectories; waits for the device). With UpdateOnDevice
+	/// this is what Navigator.UpdateTrajectory (Navigator.cs:258-262) should copy for BestParticle.</summary>
+	public List<Tuple<double, double[]>> DeviceWayPoints(int particle)
+	{
+		int length; IntPtr times, poses, slots;
+		Check(PhdHipLib.phd_trajectories(nav, new int[] {particle}, 1, out length, out times, out poses, out slots));
+		double[] t = new double[length], x = new double[7 * length];
+		if (length > 0) { Marshal.Copy(times, t, 0, length); Marshal.Copy(poses, x, 0, 7 * length); }
+		var way = new List<Tuple<double, double[]>>(length);               // TimedState
+		for (int k = 0; k < length; k++) {
+			double[] state = new double[7];
+			Array.Copy(x, 7 * k, state, 0, 7);
+			way.Add(Tuple.Create(t[k], state));
+		}
+		return way;
 	}
 
 	/// <summary>≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531) for a batch of

@@ -237,8 +237,42 @@ int           phd_particle_count(phd_navigator* nav);
 int phd_map(phd_navigator* nav, int particle, int* ncomp,
             const double** w, const double** mean3, const double** cov9);
 /* Source slot of every particle in the last step (identity when no resampling happened); the
- * host applies it to its own per-particle objects (trajectories). `resampled` <- 0/1.           */
+ * host applies it to its own per-particle objects (trajectories). `resampled` <- 0/1. It knows the LAST step only: a host
+ * that posts steps without waiting for each, or runs the motion model on the device, keeps its trajectories with the
+ * trajectory log below instead.                                                                  */
 const int32_t* phd_resample_sources(phd_navigator* nav, int* length, uint8_t* resampled);
+
+/* ---- particle trajectories on the device (Vehicle.WayPoints per particle: Vehicle.cs:335, TrackVehicle.cs:101, deep-copied
+ * with the vehicle by ResampleParticles, PHDNavigator.cs:740) -------------------------------------------------------------
+ * An opt-in log per handle of the particle poses and of who descends from whom, written on the handle's stream without a
+ * host wait. Its meaning is the reference's, as a list per particle: an append pushes (i, pose of particle i) onto
+ * particle i's list; a step that resampled replaces the lists by new[i] = copy(old[source[i]]). A step that did not
+ * resample, a dropped step (PHD_ERR_CAPACITY / PHD_ERR_ASSOCIATION, and the steps queued behind it until phd_sync) and a
+ * step in frozen mode (phd_set_frozen) change nothing. Off (the default) a step launches nothing for it.
+ *
+ * phd_history_enable  `capacity` entries (frames); 0 switches the log off and frees it. Every call restarts the log at
+ *                     length 0 (that is also how a host does ResetHistory) and waits for the handle's streams. Memory:
+ *                     capacity * max_particles * 60 bytes (7 doubles and one slot per particle and entry) and a few words
+ *                     per entry and particle more. A failed allocation is PHD_ERR_DEVICE and leaves the log off. Refused
+ *                     with PHD_ERR_BAD_ARGUMENT on a multi-device handle; while the log is on, phd_step_local_async and
+ *                     phd_step_global[_device]_async are refused the same way (sharded ancestry is not kept).
+ * phd_history_append  one entry: the current particle poses and, for every slot, the slot its particle held in the
+ *                     previous entry. Asynchronous like phd_update_motion (enqueued on the handle's stream, the bank of
+ *                     the current state is looked up on the device): correct right behind phd_step_async and
+ *                     phd_update_motion. `time` is kept on the host. A full log: PHD_ERR_CAPACITY at once, nothing is
+ *                     enqueued and the log is as it was (it does not grow in place: enable a larger one). A log that is
+ *                     off: PHD_ERR_BAD_ARGUMENT.
+ * phd_trajectories    the paths of `nparticles` particles of the CURRENT state (indices into it; out of range:
+ *                     PHD_ERR_BAD_ARGUMENT), oldest entry first, resamplings since the last append included:
+ *                     *length entries; times[length]; poses7[nparticles][length][7]; slots[nparticles][length], the slot
+ *                     the ancestor held at that entry. Library-owned buffers, valid until the next call on the handle.
+ *                     Waits for the device. The cost follows the number of entries at which a resampling happened, not
+ *                     the length of the path (plus the copy of the path itself).
+ * phd_reset and phd_upload_state_soa restart the log (length 0, capacity kept).                                        */
+int phd_history_enable(phd_navigator* nav, int capacity);
+int phd_history_append(phd_navigator* nav, double time);
+int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticles, int* length,
+                     const double** times, const double** poses7, const int32_t** slots);
 
 /* Stage-level entry points for the unit KATs (the stages behind PHDNavigator's public methods).
  *   phd_stage_run(z, with_alpha)  runs predict -> correct -> prune (-> alpha) on EVERY particle of the handle's state, without

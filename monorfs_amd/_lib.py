@@ -9,7 +9,7 @@ from .abi import PhdParams
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("PHDHIP_SO") or os.path.join(CSRC, "libphdhip.so")   # (PHDHIP_SO: another build of the same library, for A/B timing)
-SOURCES = ["phdhip.hip", "phd_multi.inc", "phd_kernels.h", "phd_correct.h", "phd_sweep.h", "phd_prune.h", "phd_alpha.h", "phd_resample.h", "phd_device.h"]
+SOURCES = ["phdhip.hip", "phd_multi.inc", "phd_kernels.h", "phd_correct.h", "phd_sweep.h", "phd_prune.h", "phd_alpha.h", "phd_resample.h", "phd_history.h", "phd_device.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 
 dp = C.POINTER(C.c_double)
@@ -93,6 +93,9 @@ def load():
         "phd_particle_count": (C.c_int, [P]),
         "phd_map": (C.c_int, [P, C.c_int, ip, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
         "phd_resample_sources": (ip, [P, ip, u8p]),
+        "phd_history_enable": (C.c_int, [P, C.c_int]),
+        "phd_history_append": (C.c_int, [P, C.c_double]),
+        "phd_trajectories": (C.c_int, [P, ip, C.c_int, C.POINTER(C.c_int), C.POINTER(dp), C.POINTER(dp), C.POINTER(ip)]),
         "phd_stage_run": (C.c_int, [P, dp, C.c_int, C.c_uint8]),
         "phd_stage_map": (C.c_int, [P, C.c_int, C.c_int, ip, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
         "phd_stage_alpha": (dp, [P, ip]),
@@ -141,4 +144,5 @@ EXPORTS = ["phd_api_version", "phd_default_params", "phd_create", "phd_create_mu
            "phd_plan_migration", "phd_test_migration_plan", "phd_multi_report", "phd_last_resampled", "phd_migration_send_buffer", "phd_migration_recv_buffer", "phd_migration_pack_async",
            "phd_migration_unpack_async", "phd_device_gather_buffer", "phd_step_global_device_async", "phd_migration_ipc_export", "phd_migration_ipc_open",
            "phd_migration_set_peers", "phd_migration_recv_is_finegrained", "phd_migration_push_async", "phd_migration_set_landing", "phd_stream", "phd_set_stream", "phd_timing_reset", "phd_last_timings", "phd_last_timing_counts", "phd_upload_state_soa",
-           "phd_download_state_soa", "phd_set_depth_map", "phd_test_detection_probability"]
+           "phd_download_state_soa", "phd_set_depth_map", "phd_test_detection_probability",
+           "phd_history_enable", "phd_history_append", "phd_trajectories"]

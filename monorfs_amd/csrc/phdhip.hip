@@ -5,6 +5,7 @@
 // PHD_ERR_NO_DEVICE and every other entry point needs a handle.
 #include "../../include/phdhip.h"
 #include "phd_kernels.h"
+#include "phd_history.h"
 
 #include <algorithm>
 #include <atomic>
@@ -175,6 +176,15 @@ struct phd_navigator {
 	DevBuf<double> d_graw; int grawcap = 0;          // per-rank host: the all-gather's landing buffer, [world][P + 1] (weights | status word)
 	std::vector<void*> ipc_opened;                   // peers' receive buffers opened with hipIpcOpenMemHandle (closed in phd_destroy)
 	bool plan_on_device = false;                     // the last global step left its plan on the device only (phd_step_global_device_async)
+	// the trajectory log (phd_history_enable; phd_history.h): hist_cap entries of Pcap particles, hist_len of them written; hist_pp:
+	// which copy of pend is current (flipped by every launch that writes the other one); the times stay on the host
+	int hist_cap = 0, hist_len = 0, hist_pp = 0;
+	DevBuf<double> d_hpose; DevBuf<int> d_hparent, d_hdirty, d_hpend;   // d_hpend: [2][Pcap] | the two dirty words
+	std::vector<double> h_htimes;
+	// phd_trajectories: the requested particles and the paths on the device, their pinned mirrors on the host (grown on demand)
+	DevBuf<int> d_tq, d_tslot; DevBuf<double> d_tpose; PinBuf<int> h_tq, h_tslot; PinBuf<double> h_tpose; size_t tqcap = 0, tcap = 0;
+	int* hpend(int which) { return d_hpend + (size_t) which * Pcap; }
+	int* hpdirty(int which) { return d_hpend + 2 * (size_t) Pcap + which; }
 	// host mirrors handed out by the getters
 	std::vector<double> h_weights, h_poses, h_mw, h_mm, h_mc, h_alpha, h_setll, h_tmp;
 	std::vector<int32_t> h_src;
@@ -696,6 +706,29 @@ int materialise(phd_navigator* nav)
 	return PHD_OK;
 }
 
+// The trajectory log starts again: no entries, pend the clean identity (on the handle's stream, behind whatever still reads it).
+int hist_restart(phd_navigator* nav)
+{
+	nav->hist_len = 0;
+	nav->h_htimes.clear();
+	if (nav->hist_cap < 1) return PHD_OK;
+	nav->hist_pp ^= 1;
+	hipLaunchKernelGGL(k_hist_identity, dim3((nav->Pcap + 255) / 256), dim3(256), 0, nav->stream, nav->hpend(nav->hist_pp), nav->hpdirty(nav->hist_pp), nav->Pcap);
+	HC(hipGetLastError());
+	return PHD_OK;
+}
+
+// Behind the end of a step, on the stream that ran it: the step's resampling (if it had one and was not dropped) goes into pend.
+int hist_compose(phd_navigator* nav, hipStream_t st)
+{
+	const int o = nav->hist_pp, n = o ^ 1;
+	hipLaunchKernelGGL(k_hist_compose, dim3((nav->P + 255) / 256), dim3(256), 0, st, (const int*) nav->d_flags, (const int*) nav->d_info, (const int*) nav->d_src,
+	                   (const int*) nav->hpend(o), (const int*) nav->hpdirty(o), nav->hpend(n), nav->hpdirty(n), nav->P);
+	HC(hipGetLastError());
+	nav->hist_pp = n;
+	return PHD_OK;
+}
+
 }  // namespace
 
 // ---- multi-device handle (phd_create_multi, phd_multi.inc): every entry point that means something for it dispatches here
@@ -719,6 +752,7 @@ void multi_destroy(phd_navigator* nav);
 phd_navigator* multi_shard0(phd_navigator* nav);
 static void multi_timing_reset(phd_navigator* nav, uint8_t enabled);
 #define MULTI_UNSUPPORTED(nav, what) if ((nav) && (nav)->multi) return (nav)->fail(PHD_ERR_BAD_ARGUMENT, what ": not available on a multi-device handle (use a single-device handle)")
+#define HISTORY_UNSUPPORTED(nav, what) if ((nav) && (nav)->hist_cap > 0) return (nav)->fail(PHD_ERR_BAD_ARGUMENT, what ": not available while the trajectory log is on (phd_history_enable(nav, 0) switches it off; sharded ancestry is not kept)")
 
 // =================================================================================================
 extern "C" {
@@ -996,7 +1030,7 @@ static int reset_impl(phd_navigator* nav, int nparticles, const double* pose7, c
 	nav->h_info[0] = 0; nav->h_info[1] = 0;   // BestParticle = 0 (:265)
 	HC(hipMemcpy(nav->d_info, nav->h_info, 8, hipMemcpyHostToDevice));
 	nav->stage_valid = false;
-	return PHD_OK;
+	return hist_restart(nav);
 }
 
 int phd_reset(phd_navigator* nav, int nparticles, const double* pose7, const double* w, const double* mean3,
@@ -1232,7 +1266,7 @@ static int upload_impl(phd_navigator* nav, int nparticles, int stride, const dou
 	HC(hipMemcpy(nav->bank[I].weights, weights, (size_t) nparticles * 8, hipMemcpyHostToDevice));
 	nav->P = nparticles;
 	nav->stage_valid = false;
-	return PHD_OK;
+	return hist_restart(nav);
 }
 
 int phd_upload_state_soa(phd_navigator* nav, int nparticles, int stride, const double* planes, const int32_t* counts,
@@ -1449,6 +1483,10 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 			                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE, L);
 		}
 		if (rc) { nav->pipe_ok = false; return rc; }
+		if (nav->hist_cap > 0 && !nav->frozen) {
+			rc = hist_compose(nav, L);
+			if (rc) { nav->pipe_ok = false; return rc; }
+		}
 		HC(hipEventRecord(nav->ev_res, L));
 		HC(hipStreamWaitEvent(X, nav->ev_res, 0));
 		nav->lagger ^= 1;
@@ -1465,6 +1503,10 @@ int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample)
 			                      nav->d_sel + (nav->parity ^ 1) * SEL_STRIDE);
 		}
 		if (rc) return rc;
+		if (nav->hist_cap > 0 && !nav->frozen) {
+			rc = hist_compose(nav, nav->stream);
+			if (rc) return rc;
+		}
 	}
 	nav->parity ^= 1;
 	nav->stage_valid = false;
@@ -1566,6 +1608,102 @@ const int32_t* phd_resample_sources(phd_navigator* nav, int* length, uint8_t* re
 	if (length) *length = nav->P;
 	if (resampled) *resampled = nav->h_info[1] ? 1 : 0;
 	return nav->h_src.data();
+}
+
+// ---- the trajectory log (phd_history.h) ---------------------------------------------------------
+int phd_history_enable(phd_navigator* nav, int capacity)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_history_enable");
+	if (capacity < 0) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_history_enable: capacity is the number of entries, 0 switches the log off");
+	if (nav->sharded_used) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_history_enable: this handle runs sharded steps (sharded ancestry is not kept)");
+	enter(nav);
+	// (kernels of posted steps may still write the buffers that go)
+	HC(hipStreamSynchronize(nav->stream));
+	for (int s = 0; s < phd_navigator::MAXSPLIT - 1; s++) if (nav->aux[s]) HC(hipStreamSynchronize(nav->aux[s]));
+	nav->hist_cap = 0; nav->hist_len = 0; nav->h_htimes.clear();
+	nav->d_hpose.reset(); nav->d_hparent.reset(); nav->d_hdirty.reset(); nav->d_hpend.reset();
+	if (capacity == 0) return PHD_OK;
+	const size_t rows = (size_t) capacity * nav->Pcap;
+	hipError_t e = nav->d_hpose.alloc(rows * 7);
+	if (e == hipSuccess) e = nav->d_hparent.alloc(rows);
+	if (e == hipSuccess) e = nav->d_hdirty.alloc(capacity);
+	if (e == hipSuccess) e = nav->d_hpend.alloc(2 * (size_t) nav->Pcap + 2);
+	if (e == hipSuccess) e = hipMemsetAsync(nav->d_hdirty, 0, (size_t) capacity * 4, nav->stream);
+	if (e != hipSuccess) {
+		(void) hipGetLastError();
+		nav->d_hpose.reset(); nav->d_hparent.reset(); nav->d_hdirty.reset(); nav->d_hpend.reset();
+		return nav->fail(PHD_ERR_DEVICE, std::string("phd_history_enable: ") + std::to_string(rows * 60) + " bytes for the log: " + hipGetErrorString(e));
+	}
+	nav->hist_cap = capacity;
+	nav->hist_pp = 0;
+	return hist_restart(nav);
+}
+
+int phd_history_append(phd_navigator* nav, double time)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_history_append");
+	if (nav->hist_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_history_append: the trajectory log is off (phd_history_enable)");
+	if (nav->P < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_history_append: no particles (call phd_reset first)");
+	if (nav->hist_len >= nav->hist_cap) return nav->fail(PHD_ERR_CAPACITY, "phd_history_append: the trajectory log is full (" + std::to_string(nav->hist_cap) + " entries)");
+	enter(nav);
+	const int k = nav->hist_len, o = nav->hist_pp, n = o ^ 1;
+	const size_t row = (size_t) k * nav->Pcap;
+	StepBufs b = make_bufs(nav);
+	hipLaunchKernelGGL(k_hist_append, dim3((nav->P * 7 + 255) / 256), dim3(256), 0, nav->stream, b, nav->P, nav->d_hpose + row * 7, nav->d_hparent + row, nav->d_hdirty + k,
+	                   (const int*) nav->hpend(o), (const int*) nav->hpdirty(o), nav->hpend(n), nav->hpdirty(n));
+	HC(hipGetLastError());
+	nav->hist_pp = n;
+	nav->hist_len = k + 1;
+	nav->h_htimes.push_back(time);
+	return PHD_OK;
+}
+
+int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticles, int* length, const double** times, const double** poses7, const int32_t** slots)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_trajectories");
+	if (nav->hist_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories: the trajectory log is off (phd_history_enable)");
+	if (!particles || nparticles < 1 || !length) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories: a list of at least one particle and `length`");
+	for (int i = 0; i < nparticles; i++) {
+		if (particles[i] < 0 || particles[i] >= nav->P) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories: particle " + std::to_string(particles[i]) + " out of range");
+	}
+	enter(nav);
+	const int L = nav->hist_len;
+	const size_t cells = std::max((size_t) nparticles * L, (size_t) 1);
+	if ((size_t) nparticles > nav->tqcap) {
+		nav->tqcap = 0;
+		HC(nav->d_tq.alloc(nparticles));
+		HC(nav->h_tq.alloc(nparticles, hipHostMallocDefault));
+		nav->tqcap = nparticles;
+	}
+	if (cells > nav->tcap) {
+		const size_t want = std::max(cells, nav->tcap + nav->tcap / 2);
+		nav->tcap = 0;
+		nav->d_tpose.reset(); nav->d_tslot.reset(); nav->h_tpose.reset(); nav->h_tslot.reset();   // (the old ones go first: the buffers can be large)
+		HC(nav->d_tpose.alloc(want * 7));
+		HC(nav->d_tslot.alloc(want));
+		HC(nav->h_tpose.alloc(want * 7, hipHostMallocDefault));
+		HC(nav->h_tslot.alloc(want, hipHostMallocDefault));
+		nav->tcap = want;
+	}
+	if (L > 0) {
+		std::memcpy(nav->h_tq, particles, (size_t) nparticles * 4);
+		HC(hipMemcpyAsync(nav->d_tq, nav->h_tq, (size_t) nparticles * 4, hipMemcpyHostToDevice, nav->stream));
+		const int o = nav->hist_pp;
+		hipLaunchKernelGGL(k_hist_trace, dim3((nparticles + 3) / 4), dim3(256), 0, nav->stream, (const double*) nav->d_hpose, (const int*) nav->d_hparent, (const int*) nav->d_hdirty,
+		                   (const int*) nav->hpend(o), (const int*) nav->hpdirty(o), (const int*) nav->d_tq, nparticles, L, nav->P, nav->Pcap, (double*) nav->d_tpose, (int*) nav->d_tslot);
+		HC(hipGetLastError());
+		HC(hipMemcpyAsync(nav->h_tpose, nav->d_tpose, (size_t) nparticles * L * 7 * 8, hipMemcpyDeviceToHost, nav->stream));
+		HC(hipMemcpyAsync(nav->h_tslot, nav->d_tslot, (size_t) nparticles * L * 4, hipMemcpyDeviceToHost, nav->stream));
+	}
+	HC(hipStreamSynchronize(nav->stream));
+	*length = L;
+	if (times) *times = nav->h_htimes.data();
+	if (poses7) *poses7 = nav->h_tpose;
+	if (slots) *slots = nav->h_tslot;
+	return PHD_OK;
 }
 
 // ---- stage-level entry points ------------------------------------------------------------------
@@ -1919,6 +2057,7 @@ int phd_step_local_async(phd_navigator* nav, uint8_t onlymapping)
 {
 	if (!nav) return PHD_ERR_BAD_ARGUMENT;
 	MULTI_UNSUPPORTED(nav, "phd_step_local_async");
+	HISTORY_UNSUPPORTED(nav, "phd_step_local_async");
 	return step_local(nav, onlymapping);
 }
 
@@ -2024,6 +2163,7 @@ int phd_step_global_async(phd_navigator* nav, int rank, int world_size, double u
 {
 	if (!nav) return PHD_ERR_BAD_ARGUMENT;
 	MULTI_UNSUPPORTED(nav, "phd_step_global_async");
+	HISTORY_UNSUPPORTED(nav, "phd_step_global_async");
 	if (world_size < 1 || world_size > PHD_MAX_DEVICES || rank < 0 || rank >= world_size) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_global: bad rank/world (at most 64 ranks)");
 	return step_global(nav, rank, world_size, u_resample, 0, true);
 }
@@ -2059,6 +2199,7 @@ int phd_step_global_device_async(phd_navigator* nav, int rank, int world_size, d
 {
 	if (!nav) return PHD_ERR_BAD_ARGUMENT;
 	MULTI_UNSUPPORTED(nav, "phd_step_global_device_async");
+	HISTORY_UNSUPPORTED(nav, "phd_step_global_device_async");
 	if (world_size < 1 || world_size > PHD_MAX_DEVICES || rank < 0 || rank >= world_size) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_global_device: bad rank/world (at most 64 ranks)");
 	if (!nav->d_graw || nav->grawcap < world_size * (nav->P + 1)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_global_device: no gather buffer (phd_device_gather_buffer(world_size) first)");
 	if (!nav->peers_set && world_size > 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_global_device: the peers' receive buffers are not known (phd_migration_ipc_open / phd_migration_set_peers first)");

@@ -79,6 +79,50 @@ public:
 	{
 		check(phd_update_motion(nav_, reading.data(), noise.empty() ? nullptr : noise[0].data(), ParticleCount, perfectstill ? 1 : 0));
 	}
+	// ... with the frame's time: the same, and its waypoint when the trajectory log is on (Vehicle.Update, Vehicle.cs:335)
+	void UpdateOdometry(double time, const std::array<double, 6>& reading, const std::vector<std::array<double, 6>>& noise, bool perfectstill)
+	{
+		UpdateOdometry(reading, noise, perfectstill);
+		if (history_) appendHistory(time);
+	}
+
+	// The particles' paths on the device (phd_history_enable): room for `capacity` entries, 0 switches the log off; every
+	// call restarts it at length 0 (ResetHistory)
+	void enableHistory(int capacity)
+	{
+		check(phd_history_enable(nav_, capacity));
+		history_ = capacity > 0;
+	}
+
+	// one entry: the current particle poses (phd_history_append; asynchronous)
+	void appendHistory(double time) { check(phd_history_append(nav_, time)); }
+
+	// ≙ VehicleParticles[i].WayPoints (Vehicle.cs:141) of the listed particles of the current state, oldest entry first
+	// (phd_trajectories; waits for the device): Times[L], Poses[n][L], Slots[n][L] — the slot the ancestor held at that entry
+	struct Trajectories {
+		std::vector<double> Times;
+		std::vector<std::vector<Pose3D>> Poses;
+		std::vector<std::vector<int32_t>> Slots;
+	};
+	Trajectories WayPoints(const std::vector<int32_t>& particles)
+	{
+		int L = 0;
+		const double *t = nullptr, *x = nullptr;
+		const int32_t* s = nullptr;
+		check(phd_trajectories(nav_, particles.data(), (int) particles.size(), &L, &t, &x, &s));
+		Trajectories out;
+		out.Times.assign(t, t + (L > 0 ? L : 0));
+		out.Poses.assign(particles.size(), std::vector<Pose3D>(L));
+		out.Slots.assign(particles.size(), std::vector<int32_t>(L));
+		for (size_t j = 0; j < particles.size(); j++) {
+			for (int k = 0; k < L; k++) {
+				const double* q = x + (j * L + k) * 7;
+				std::copy(q, q + 7, out.Poses[j][k].begin());
+				out.Slots[j][k] = s[j * L + k];
+			}
+		}
+		return out;
+	}
 
 	// ≙ static QuasiSetLogLikelihood(measurements, map, pose) (:526-531), for a batch of candidate poses (row f4)
 	std::vector<double> QuasiSetLogLikelihood(const std::vector<PixelRangeMeasurement>& measurements,
@@ -231,6 +275,7 @@ private:
 	}
 
 	phd_navigator* nav_ = nullptr;
+	bool history_ = false;   // the trajectory log is on: UpdateOdometry(time, ...) appends
 };
 
 }  // namespace monorfs

@@ -67,6 +67,7 @@ class PHDNavigator:
             self._h = self._lib.phd_create(C.byref(self.params), device)
         if not self._h:
             raise PHDError(-1, self._lib.phd_create_error().decode())
+        self._history, self._history_len = False, 0   # the trajectory log is on | its entries (the library's count, mirrored)
         self.ParticleCount = particlecount
         self.OnlyMapping = bool(onlymapping)
         n = 1 if onlymapping else particlecount   # :201-203
@@ -96,6 +97,7 @@ class PHDNavigator:
         w, m, c = (np.ascontiguousarray(x, np.float64) for x in model)
         pose = np.ascontiguousarray(pose, np.float64)
         self._check(self._lib.phd_reset(self._h, int(particlecount), _ptr(pose), _ptr(w), _ptr(m), _ptr(c), len(w)))
+        self._history_len = 0   # (the library restarts the log)
 
     def CollapseParticles(self, particlecount):
         """≙ :233-236: every particle becomes a copy of the best one."""
@@ -137,6 +139,7 @@ class PHDNavigator:
         _, P, stride = planes.shape
         self._check(self._lib.phd_upload_state_soa(self._h, P, stride, _ptr(planes), counts.ctypes.data_as(ip),
                                                    _ptr(poses), _ptr(weights)))
+        self._history_len = 0
 
     def download_state(self, stride):
         P = self.particle_count
@@ -160,6 +163,8 @@ class PHDNavigator:
         """≙ PHDNavigator.Update (:295-314). The motion model and its RNG stay on the host
         (TrackVehicle.UpdateNoisy): the caller hands over the propagated particle poses."""
         self.set_poses(poses)
+        if self._history:
+            self.append_history(time)
 
     def UpdateOdometry(self, time, reading, noise=None, perfect_still=False):
         """≙ PHDNavigator.Update (:295-314) with the motion step on the device (phd_update_motion):
@@ -172,6 +177,41 @@ class PHDNavigator:
                 raise ValueError("one noise vector per particle")
         self._check(self._lib.phd_update_motion(self._h, _ptr(reading), _ptr(noise) if noise is not None else None,
                                                 self.particle_count, int(bool(perfect_still))))
+        if self._history:
+            self.append_history(time)
+
+    # ------------------------------------------------------------------ trajectories (Vehicle.WayPoints per particle)
+    def enable_history(self, capacity):
+        """The trajectory log on the device (phd_history_enable): room for `capacity` entries, one per Update / UpdateOdometry
+        from now on; 0 switches it off. Every call restarts the log at length 0 (ResetHistory)."""
+        self._check(self._lib.phd_history_enable(self._h, int(capacity)))
+        self._history = int(capacity) > 0
+        self._history_len = 0
+
+    def append_history(self, time=None):
+        """One entry of the log: the current particle poses (phd_history_append; asynchronous). time=None: the entry's index."""
+        if time is None:
+            time = float(self.history_length)
+        self._check(self._lib.phd_history_append(self._h, float(time)))
+        self._history_len += 1
+
+    @property
+    def history_length(self):
+        return self._history_len if self._history else 0
+
+    def WayPoints(self, particles):
+        """≙ VehicleParticles[i].WayPoints (Vehicle.cs:141) for the listed particles of the current state, as the reference's
+        deep copies in ResampleParticles (:740) leave them: (times[L], poses[n][L][7], slots[n][L]), oldest entry first;
+        slots[j][k] is the slot the ancestor of particles[j] held at entry k (phd_trajectories; waits for the device)."""
+        q = np.ascontiguousarray(list(particles) if not isinstance(particles, np.ndarray) else particles, np.int32).reshape(-1)
+        n = C.c_int(0)
+        t, x, s = dp(), dp(), ip()
+        self._check(self._lib.phd_trajectories(self._h, q.ctypes.data_as(ip), len(q), C.byref(n), C.byref(t), C.byref(x), C.byref(s)))
+        L = n.value
+        if L == 0:
+            return np.zeros(0), np.zeros((len(q), 0, 7)), np.zeros((len(q), 0), np.int32)
+        return (np.ctypeslib.as_array(t, shape=(L,)).copy(), np.ctypeslib.as_array(x, shape=(len(q) * L * 7,)).reshape(len(q), L, 7).copy(),
+                np.ctypeslib.as_array(s, shape=(len(q) * L,)).reshape(len(q), L).copy())
 
     def QuasiSetLogLikelihood(self, measurements, landmarks, poses):
         """≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531), batched over

@@ -3,11 +3,16 @@
 drives the C# solver with `-i=record` drives PHDNavigator here, and estimate.out / maps.out come back in the same
 format (Simulation.SaveToFile, Simulation.cs:391-488).
 
-    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--oracle]
+    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints]
     python scripts/replay.py --make DIR [--frames K]      # write a small synthetic record first
 
 The host keeps what the reference keeps managed: the motion noise dt * chol(Q) * N(0, I) per particle and the
-resampling uniform are drawn here (numpy), the motion step itself runs on the device (phd_update_motion)."""
+resampling uniform are drawn here (numpy), the motion step itself runs on the device (phd_update_motion).
+
+estimate.out: with --estimate poses (the default) every frame's trajectory is the list of the best poses of the frames so
+far; with --estimate waypoints it is what the reference writes, the best particle's own path (BestEstimate.WayPoints,
+copied by Navigator.UpdateTrajectory, Navigator.cs:258-262), read from the trajectory log on the device
+(phd_history_enable / phd_trajectories). The two differ whenever a step resamples or the best particle changes."""
 import argparse
 import os
 import sys
@@ -54,26 +59,48 @@ class DeviceSolver:
         b = self.nav.BestParticle
         return self.nav.poses()[b], self.nav.MapModel(b)
 
+    def start_waypoints(self, capacity):
+        """the trajectory log, with entry 0 at time 0 as Vehicle's constructor leaves it (Vehicle.cs:228)"""
+        self.nav.enable_history(capacity)
+        self.nav.append_history(0.0)
 
-def replay(rec, particles, seed, solver_cls):
+    def step_waypoints(self, time, reading, noise, z, u):
+        """PHDNavigator.Update (:295-314): the motion step, its waypoint, then UpdateTrajectory's copy of BestEstimate.WayPoints
+        (:313) — BestParticle is still the one the previous SlamUpdate left — and only then this frame's SlamUpdate"""
+        self.nav.UpdateOdometry(time, reading, noise)   # (appends: the log is on)
+        times, poses, _ = self.nav.WayPoints([self.nav.BestParticle])
+        if len(z):
+            self.nav.SlamUpdate(time, z, u_resample=u)
+        return (times, poses[0]), self.nav.MapModel(self.nav.BestParticle)
+
+
+def replay(rec, particles, seed, solver_cls, estimate="poses"):
+    if estimate not in ("poses", "waypoints"):
+        raise ValueError("estimate is 'poses' or 'waypoints'")
     frames = frames_of(rec)
     p, pose = params_of(rec, particles, max(len(z) for _, _, z in frames))
     solver = solver_cls(p, pose, particles)
+    if estimate == "waypoints":
+        solver.start_waypoints(len(frames) + 1)
     rng = np.random.default_rng(seed)
     cfg = config_of(rec)
     chol = np.linalg.cholesky(cfg["MotionCovarianceMultiplier"] * np.array(cfg["MotionCovariance"], float))   # PHDNavigator.cs:257-259
-    trajectory, estimate, maps = [], [], []
+    trajectory, history, maps = [], [], []
     tprev = frames[0][0]
     for t, reading, z in frames:
         dt = t - tprev
         tprev = t
         noise = dt * (rng.normal(size=(particles, 6)) @ chol.T)     # Util.RandomGaussianVector, Util.cs:173-202
         u = float(rng.uniform(1e-6, 1.0))
-        bpose, bmap = solver.step(reading, noise, z, u)
-        trajectory.append((t, bpose))
-        estimate.append((t, list(trajectory)))
+        if estimate == "waypoints":
+            (wt, wp), bmap = solver.step_waypoints(t, reading, noise, z, u)
+            history.append((t, [(float(a), np.array(b)) for a, b in zip(wt, wp)]))
+        else:
+            bpose, bmap = solver.step(reading, noise, z, u)
+            trajectory.append((t, bpose))
+            history.append((t, list(trajectory)))
         maps.append((t, bmap))
-    return {"estimate.out": rio.serialize_trajectories(estimate), "maps.out": rio.serialize_maps(maps)}
+    return {"estimate.out": rio.serialize_trajectories(history), "maps.out": rio.serialize_maps(maps)}
 
 
 def make_synthetic_record(path, frames=12, landmarks=14, seed=3):
@@ -119,13 +146,14 @@ def main():
     ap.add_argument("--particles", type=int, default=32)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out")
+    ap.add_argument("--estimate", choices=("poses", "waypoints"), default="poses")
     a = ap.parse_args()
     if a.make:
         print("wrote", make_synthetic_record(a.make, a.frames))
         if not a.record:
             return
     rec = rio.read_record(a.record)
-    out = replay(rec, a.particles, a.seed, DeviceSolver)
+    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate)
     if a.out:
         rio.write_record(a.out, dict(rec, **out))
     maps = rio.map_history_from_descriptor(out["maps.out"])

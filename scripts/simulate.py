@@ -6,7 +6,11 @@ view, N(0, R) noise, Poisson clutter), the particles take the noisy odometry (ph
 (phd_slam_update), and the run is written as a record (Simulation.SaveToFile) that `-i=record` / scripts/replay.py can
 replay. The random streams are numpy's, not AForge's: runs are statistically, not bitwise, those of the C# program.
 
-    python scripts/simulate.py scene.world moves.in --out run/ [--config x.cfg] [--particles 20] [--seed 1]"""
+    python scripts/simulate.py scene.world moves.in --out run/ [--config x.cfg] [--particles 20] [--seed 1] [--estimate poses|waypoints]
+
+estimate.out is the list of the best poses frame by frame (--estimate poses, the default) or, with --estimate waypoints, the best
+particle's own path as the reference records it (Navigator.UpdateTrajectory, Navigator.cs:258-262), read from the trajectory log
+on the device; a mode switch (CollapseParticles) starts that log again."""
 import argparse
 import math
 import os
@@ -75,7 +79,9 @@ class SimulatedVehicle:
         return np.array(out, float).reshape(-1, 3)
 
 
-def simulate(scene_text, command_lines, config, particles, seed, onlymapping=False, log=None):
+def simulate(scene_text, command_lines, config, particles, seed, onlymapping=False, log=None, estimate="poses"):
+    if estimate not in ("poses", "waypoints"):
+        raise ValueError("estimate is 'poses' or 'waypoints'")
     from monorfs_amd import navigator
     rng = np.random.default_rng(seed)
     pose, measurer, landmarks = rio.scene_from_descriptor(scene_text)
@@ -86,11 +92,14 @@ def simulate(scene_text, command_lines, config, particles, seed, onlymapping=Fal
     p = rio.phd_params_from_config(config, measurer=[measurer[0], float(np.float32(measurer[1])), float(np.float32(measurer[2]))] + list(measurer[3:7]),
                                    max_particles=particles, max_measurements=max(64, 8 * len(landmarks) + 64))
     nav = navigator.PHDNavigator(p, particlecount=particles, onlymapping=onlymapping, pose=pose)
+    if estimate == "waypoints":
+        nav.enable_history(len(commands) + 1)
+        nav.append_history(0.0)                 # Vehicle's constructor (Vehicle.cs:228)
     motion_chol = np.linalg.cholesky(config["MotionCovarianceMultiplier"] * np.array(config["MotionCovariance"], float))
     frame = 1.0 / 30            # FrameElapsed (Manipulator.cs:351, 30 fps)
     measure_elapsed = config["MeasureElapsed"]
     t, last_update = 0.0, 0.0
-    trajectory, odometry, measurements, estimate, maps, tags = [(0.0, pose.copy())], [], [], [], [], []
+    trajectory, odometry, measurements, history, maps, tags = [(0.0, pose.copy())], [], [], [], [], []
     best_track = [(0.0, pose.copy())]
     for cmd in commands:
         reading = np.asarray(cmd[:6], float)
@@ -111,6 +120,9 @@ def simulate(scene_text, command_lines, config, particles, seed, onlymapping=Fal
         n = nav.particle_count
         noise = None if nav.OnlyMapping else frame * (rng.normal(size=(n, 6)) @ motion_chol.T)   # TrackVehicle.UpdateNoisy
         nav.UpdateOdometry(t, corrupt, noise, perfect_still=config["PerfectStill"])
+        if estimate == "waypoints":             # UpdateTrajectory (PHDNavigator.cs:313): BestParticle is the previous SlamUpdate's
+            wt, wp, _ = nav.WayPoints([nav.BestParticle])
+            best_way = [(float(a), np.array(b)) for a, b in zip(wt, wp[0])]
         trajectory.append((t, explorer.pose.copy()))
         if t - last_update >= measure_elapsed - 1e-12:
             z = explorer.measure()
@@ -118,14 +130,14 @@ def simulate(scene_text, command_lines, config, particles, seed, onlymapping=Fal
             nav.SlamUpdate(t, z, u_resample=float(rng.uniform(1e-9, 1.0)))
             last_update = t
         best_track.append((t, nav.BestEstimate))
-        estimate.append((t, list(best_track)))
+        history.append((t, best_way if estimate == "waypoints" else list(best_track)))
         maps.append((t, nav.BestMapModel))
         if log:
             log("t = %.3f: %d measurements, %d particles, %d components in the best map" % (t, len(measurements[-1][1]) if measurements else 0, nav.particle_count, len(maps[-1][1][0])))
     nav.close()
     return {"scene.world": scene_text, "trajectory.out": rio.serialize_timed_array(trajectory),
             "odometry.out": rio.serialize_timed_array(odometry), "measurements.out": rio.serialize_measurements(measurements),
-            "estimate.out": rio.serialize_trajectories(estimate), "maps.out": rio.serialize_maps(maps),
+            "estimate.out": rio.serialize_trajectories(history), "maps.out": rio.serialize_maps(maps),
             "tags.out": rio.serialize_tags(tags), "config.cfg": rio.serialize_config(config)}
 
 
@@ -138,6 +150,7 @@ def main():
     ap.add_argument("--particles", type=int, default=20)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--onlymapping", action="store_true")
+    ap.add_argument("--estimate", choices=("poses", "waypoints"), default="poses")
     args = ap.parse_args()
     config = rio.default_config()
     if args.config:
@@ -147,7 +160,7 @@ def main():
         scene = fh.read()
     with open(args.commands) as fh:
         commands = [l for l in fh.read().splitlines() if l.strip()]
-    rec = simulate(scene, commands, config, args.particles, args.seed, args.onlymapping, log=print)
+    rec = simulate(scene, commands, config, args.particles, args.seed, args.onlymapping, log=print, estimate=args.estimate)
     rio.write_record(args.out, rec)
     print("record written to", args.out)
 
