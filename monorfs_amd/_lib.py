@@ -9,7 +9,7 @@ from .abi import PhdParams
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("PHDHIP_SO") or os.path.join(CSRC, "libphdhip.so")   # (PHDHIP_SO: another build of the same library, for A/B timing)
-SOURCES = ["phdhip.hip", "phd_multi.inc", "phd_kernels.h", "phd_correct.h", "phd_sweep.h", "phd_prune.h", "phd_alpha.h", "phd_resample.h", "phd_history.h", "phd_device.h"]
+SOURCES = ["phdhip.hip", "phd_multi.inc", "phd_kernels.h", "phd_correct.h", "phd_sweep.h", "phd_prune.h", "phd_alpha.h", "phd_resample.h", "phd_shard.h", "phd_history.h", "phd_device.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 
 dp = C.POINTER(C.c_double)

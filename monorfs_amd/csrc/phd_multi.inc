@@ -549,7 +549,7 @@ int multi_sync(phd_navigator* nav)
 		if (!rc && a->plan.counts && a->sharded_used) {   // what the device plan of the last step said
 			int st = MIG_OK;
 			hipSetDevice(a->device);
-			if (hipMemcpy(&st, a->plan.counts + 2 * m->n + 2, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = a->fail(PHD_ERR_DEVICE, "reading the migration plan's status failed");
+			if (hipMemcpy(&st, a->plan.counts + mig_word(m->n, MC_STATUS), 4, hipMemcpyDeviceToHost) != hipSuccess) rc = a->fail(PHD_ERR_DEVICE, "reading the migration plan's status failed");
 			else if (st == MIG_BAD) rc = a->fail(PHD_ERR_GENERIC, "the gathered source vector was not a resampling result");
 			else if (st == MIG_OVERFLOW) rc = a->fail(PHD_ERR_CAPACITY, "more migrating particles than the send list holds");
 		}

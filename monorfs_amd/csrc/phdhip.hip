@@ -23,7 +23,6 @@
 #include <vector>
 
 #define DSPLIT_ROWS 1024     // particles the helpers' words are allocated for (k_particle_chain with helper workgroups)
-#define PHD_MAX_DEVICES 64   // device ordinals a process may hand to phd_create / phd_create_multi
 
 namespace {
 
@@ -1528,7 +1527,8 @@ int phd_sync(phd_navigator* nav)
 	if (!rc && nav->plan_on_device && nav->sharded_used) {
 		// the host never saw the plan of the last sharded step: what it said (a flag on another rank drops the step here too)
 		int st[2] = {MIG_OK, 0};
-		HC(hipMemcpy(st, nav->plan.counts + 2 * nav->world + 2, 8, hipMemcpyDeviceToHost));
+		static_assert(MC_RESAMPLED == MC_STATUS + 1, "read together");
+		HC(hipMemcpy(st, nav->plan.counts + mig_word(nav->world, MC_STATUS), 8, hipMemcpyDeviceToHost));
 		nav->h_info[1] = st[1];
 		if (st[0] == MIG_DROPPED) rc = nav->fail(PHD_ERR_GENERIC, "the step was dropped: another rank raised a flag (its phd_sync says which); the state is the one before the step");
 		else if (st[0] == MIG_BAD) rc = nav->fail(PHD_ERR_GENERIC, "the gathered source vector was not a resampling result (were the weights of all ranks gathered?)");
@@ -1966,18 +1966,19 @@ static void free_sharded(phd_navigator* nav)
 	nav->sharded_ready = false;
 }
 
+// ints of one set of the grid plan's accumulators: cnt [64][64] | used [Pcap / 32 + 1] | bad [1]
+static size_t plan_grid_set_words(const phd_navigator* nav) { return (size_t) PHD_MAX_DEVICES * PHD_MAX_DEVICES + (size_t) (nav->Pcap + 31) / 32 + 2; }
+
 static int ensure_sharded(phd_navigator* nav, bool need_send = true)
 {
 	if (nav->sharded_ready) {
 		if (need_send && !nav->d_send) {   // (a handle first used without a send buffer: push-only hosts never need one)
-			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
 			enter(nav);
-			HC(nav->d_send.alloc((size_t) nav->sendrecs * rec));
+			HC(nav->d_send.alloc((size_t) nav->sendrecs * mig_rec_doubles(nav->cap)));
 		}
 		return PHD_OK;
 	}
 	enter(nav);
-	const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
 	nav->plan.sendcap = nav->Pcap + PHD_MAX_DEVICES;
 	nav->recvrecs = nav->Pcap;
 	nav->sendrecs = nav->plan.sendcap;
@@ -1994,27 +1995,26 @@ static int ensure_sharded(phd_navigator* nav, bool need_send = true)
 	want(nav->plan_fslot.alloc(nav->Pcap));
 	want(nav->plan_sendlist.alloc(nav->plan.sendcap));
 	want(nav->plan_senddst.alloc(nav->plan.sendcap));
-	want(nav->plan_counts.alloc(2 * PHD_MAX_DEVICES + 8));
+	want(nav->plan_counts.alloc(MIG_COUNT_WORDS));
 	nav->plan = MigPlan{nav->plan_code, nav->plan_fslot, nav->plan_sendlist, nav->plan_senddst, nav->plan_counts, nav->plan.sendcap};
-	if (e == hipSuccess) want(hipMemset(nav->plan.counts, 0, (2 * PHD_MAX_DEVICES + 8) * 4));
+	if (e == hipSuccess) want(hipMemset(nav->plan.counts, 0, MIG_COUNT_WORDS * 4));
 	// (coherent: the plan kernel's system-scope stores must reach the polling host while the kernel runs, whatever the
 	// runtime's default for mapped host memory is)
-	want(nav->h_counts.alloc(2 * PHD_MAX_DEVICES + 8, hipHostMallocMapped | hipHostMallocCoherent));
-	if (e == hipSuccess) std::memset(nav->h_counts, 0, (2 * PHD_MAX_DEVICES + 8) * 4);
+	want(nav->h_counts.alloc(MIG_COUNT_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
+	if (e == hipSuccess) std::memset(nav->h_counts, 0, MIG_COUNT_WORDS * 4);
 	want(nav->d_mslot.alloc(nav->Pcap));
-	{   // k_plan_count / k_plan_lists: [2 sets][cnt 64 x 64 | used Pcap / 32 + 1 | bad 1] | wcg [1024] | lcg [Pcap / 64 + 1]
-		const size_t set = (size_t) PHD_MAX_DEVICES * PHD_MAX_DEVICES + (size_t) (nav->Pcap + 31) / 32 + 2;
-		const size_t words = 2 * set + 1024 + (size_t) nav->Pcap / 64 + 2;
+	{   // k_plan_count / k_plan_lists: [2 sets] (plan_grid_set_words) | wcg [1024] | lcg [Pcap / 64 + 1]
+		const size_t words = 2 * plan_grid_set_words(nav) + 1024 + (size_t) nav->Pcap / 64 + 2;
 		want(nav->d_plang.alloc(words));
 		if (e == hipSuccess) want(hipMemset(nav->d_plang, 0, words * 4));
 	}
-	if (need_send) want(nav->d_send.alloc((size_t) nav->sendrecs * rec));   // (a shard of a multi-device handle packs straight into its peers' receive buffers)
+	if (need_send) want(nav->d_send.alloc((size_t) nav->sendrecs * mig_rec_doubles(nav->cap)));   // (a shard of a multi-device handle packs straight into its peers' receive buffers)
 	// The receive buffer is written by OTHER devices (peer stores of a multi-device handle's shards, or of other ranks'
 	// processes through IPC) and read here: fine-grained device memory, coherent between agents without cache maintenance —
 	// what RCCL allocates for its own peer-to-peer buffers. (See the head of phd_multi.inc for the visibility argument.)
 	if (e == hipSuccess) {
-		// (+ PHD_MAX_DEVICES words behind the records: the landing flags, one per sending rank — k_post_landing)
-		const size_t recv_bytes = ((size_t) nav->recvrecs * rec + PHD_MAX_DEVICES) * 8;
+		// (behind the records: the landing flags, one word per sending rank — k_post_landing)
+		const size_t recv_bytes = mig_recv_doubles(nav->recvrecs, nav->cap) * 8;
 		nav->recv_finegrained = getenv("PHD_COARSE_RECV") == nullptr &&
 		                        hipExtMallocWithFlags((void**) nav->d_recv.put(), recv_bytes, hipDeviceMallocFinegrained) == hipSuccess;
 		if (!nav->recv_finegrained) {
@@ -2022,7 +2022,7 @@ static int ensure_sharded(phd_navigator* nav, bool need_send = true)
 			(void) nav->d_recv.release();   // (whatever the failed call left in it is nothing to free)
 			want(nav->d_recv.alloc(recv_bytes / 8));
 		}
-		if (e == hipSuccess) want(hipMemset(nav->d_recv + (size_t) nav->recvrecs * rec, 0, PHD_MAX_DEVICES * 8));
+		if (e == hipSuccess) want(hipMemset(nav->d_recv + mig_landing_offset(nav->recvrecs, nav->cap), 0, PHD_MAX_DEVICES * 8));
 	}
 	if (e != hipSuccess) {
 		(void) hipGetLastError();
@@ -2085,34 +2085,55 @@ static bool plan_on_grid(const phd_navigator* nav, int Pl, int n)
 	return nav->plan_grid_min > 0 && Pg >= nav->plan_grid_min && Pg <= PLAN_GRID_MAXSLOTS && (Pl & 63) == 0 && nav->d_plang != nullptr;
 }
 
-// the accumulators of this launch pair (and the set its second launch clears for the next one)
-static PlanGrid plan_grid_next(phd_navigator* nav)
-{
-	const size_t set = (size_t) PHD_MAX_DEVICES * PHD_MAX_DEVICES + (size_t) (nav->Pcap + 31) / 32 + 2;
-	int* cur = nav->d_plang + (size_t) nav->plan_par * set;
-	int* nxt = nav->d_plang + (size_t) (nav->plan_par ^ 1) * set;
-	nav->plan_par ^= 1;
+// One turn of the grid plan's accumulator sets. The pair's set is chosen before the launches that add to it are enqueued (the
+// counting may ride in the grid resampling's last launch); the parity flips when k_plan_lists — the launch that clears the OTHER
+// set for the next pair — has been enqueued without error (enqueued()). A turn that ends before that leaves sets nobody will
+// clear: both are cleared on the stream, behind whatever was enqueued, and the parity starts over. (use = false: no turn at all —
+// the plan of this step does not run over the grid. The clearing's own result is not looked at: a stream that cannot take a memset
+// takes no further step either, and the handle's next call reports it.)
+struct PlanGridTurn {
+	phd_navigator* nav;
 	PlanGrid pg;
-	pg.cnt = cur; pg.used = (unsigned int*) (cur + PHD_MAX_DEVICES * PHD_MAX_DEVICES); pg.bad = cur + set - 1;
-	pg.cnt_next = nxt; pg.used_next = (unsigned int*) (nxt + PHD_MAX_DEVICES * PHD_MAX_DEVICES); pg.bad_next = nxt + set - 1;
-	pg.wcg = nav->d_plang + 2 * set;
-	pg.lcg = pg.wcg + 1024;
-	return pg;
-}
+	bool open;
+	PlanGridTurn(phd_navigator* nv, bool use) : nav(nv), open(use)
+	{
+		std::memset(&pg, 0, sizeof pg);
+		if (!use) return;
+		const size_t set = plan_grid_set_words(nav);
+		int* cur = nav->d_plang + (size_t) nav->plan_par * set;
+		int* nxt = nav->d_plang + (size_t) (nav->plan_par ^ 1) * set;
+		pg.cnt = cur; pg.used = (unsigned int*) (cur + PHD_MAX_DEVICES * PHD_MAX_DEVICES); pg.bad = cur + set - 1;
+		pg.cnt_next = nxt; pg.used_next = (unsigned int*) (nxt + PHD_MAX_DEVICES * PHD_MAX_DEVICES); pg.bad_next = nxt + set - 1;
+		pg.wcg = nav->d_plang + 2 * set;
+		pg.lcg = pg.wcg + 1024;
+	}
+	void enqueued() { nav->plan_par ^= 1; open = false; }
+	~PlanGridTurn()
+	{
+		if (!open) return;
+		(void) hipMemsetAsync(nav->d_plang, 0, 2 * plan_grid_set_words(nav) * 4, nav->stream);
+		nav->plan_par = 0;
+	}
+	PlanGridTurn(const PlanGridTurn&) = delete;
+	PlanGridTurn& operator=(const PlanGridTurn&) = delete;
+};
 
+// turn: the caller's, when the plan's counting was part of an earlier launch of it (`counted`); NULL: a turn of this call's own
 static int launch_plan(phd_navigator* nav, const StepBufs& b, const int* gsrc, const int* info, const int* lflags, const double* gflags,
-                       int Pl, int n, int rank, int* hostcounts, int seq, const double* gw, const PlanGrid* pgp = nullptr, bool counted = false)
+                       int Pl, int n, int rank, int* hostcounts, int seq, const double* gw, PlanGridTurn* turn = nullptr, bool counted = false)
 {
 	if (plan_on_grid(nav, Pl, n)) {
-		const PlanGrid pg = pgp ? *pgp : plan_grid_next(nav);
+		PlanGridTurn own(nav, turn == nullptr);
+		if (!turn) turn = &own;
 		const int G = (int) (((long long) Pl * n + 255) / 256);
-		if (!counted) hipLaunchKernelGGL(k_plan_count, dim3(G), dim3(256), 0, nav->stream, gsrc, info, lflags, gflags, Pl, n, rank, pg);
-		hipLaunchKernelGGL(k_plan_lists, dim3(G), dim3(256), 0, nav->stream, gsrc, info, lflags, gflags, Pl, n, rank, nav->plan, pg, hostcounts, seq, b, gw);
+		if (!counted) hipLaunchKernelGGL(k_plan_count, dim3(G), dim3(256), 0, nav->stream, gsrc, info, lflags, gflags, Pl, n, rank, turn->pg);
+		hipLaunchKernelGGL(k_plan_lists, dim3(G), dim3(256), 0, nav->stream, gsrc, info, lflags, gflags, Pl, n, rank, nav->plan, turn->pg, hostcounts, seq, b, gw);
+		HC(hipGetLastError());
+		turn->enqueued();
+		return PHD_OK;
 	}
-	else {
-		hipLaunchKernelGGL(k_plan_migration, dim3(1), dim3(1024), plan_lds_bytes(Pl, n), nav->stream, gsrc, info, lflags, gflags, Pl, n, rank, nav->plan,
-		                   hostcounts, seq, b, gw);
-	}
+	hipLaunchKernelGGL(k_plan_migration, dim3(1), dim3(1024), plan_lds_bytes(Pl, n), nav->stream, gsrc, info, lflags, gflags, Pl, n, rank, nav->plan,
+	                   hostcounts, seq, b, gw);
 	HC(hipGetLastError());
 	return PHD_OK;
 }
@@ -2138,14 +2159,12 @@ static int step_global(phd_navigator* nav, int rank, int world_size, double u, u
 	else if (!nav->gw_shared) nav->d_gflags = nullptr;   // (the host-plan path gathers the weights only: every rank answers for its own flags)
 	// (the plan over the grid: its accumulators are chosen here, its counting rides in the grid resampling's last launch when that runs)
 	const bool pgrid = plan_on_grid(nav, nav->P, world_size);
-	PlanGrid pg;
-	std::memset(&pg, 0, sizeof pg);
-	if (pgrid) pg = plan_grid_next(nav);
+	PlanGridTurn turn(nav, pgrid);   // (a return before k_plan_lists is enqueued ends it)
 	bool counted = false;
 	{
 		Timed t(nav, T_NR, nav->stream);
 		rc = launch_normalise(nav, b, nav->d_gw, Pg, u, onlymapping ? -1 : 0, onlymapping ? 1 : 0, nav->d_plan, nav->d_info, nullptr, nullptr,
-		                      from_graw ? (const double*) nav->d_graw : nullptr, nav->P, world_size, pgrid ? &pg : nullptr, rank, nav->d_gflags, &counted);
+		                      from_graw ? (const double*) nav->d_graw : nullptr, nav->P, world_size, pgrid ? &turn.pg : nullptr, rank, nav->d_gflags, &counted);
 	}
 	if (rc) return rc;
 	int* hc = nullptr;
@@ -2156,7 +2175,7 @@ static int step_global(phd_navigator* nav, int rank, int world_size, double u, u
 	}
 	Timed t(nav, T_PL, nav->stream);
 	return launch_plan(nav, b, (const int*) nav->d_plan, (const int*) nav->d_info, (const int*) nav->d_flags, nav->d_gflags, nav->P, world_size, rank, hc,
-	                   nav->plan_seq, (const double*) nav->d_gw, pgrid ? &pg : nullptr, counted);
+	                   nav->plan_seq, (const double*) nav->d_gw, pgrid ? &turn : nullptr, counted);
 }
 
 int phd_step_global_async(phd_navigator* nav, int rank, int world_size, double u_resample)
@@ -2240,7 +2259,7 @@ int phd_migration_ipc_export(phd_navigator* nav, void* handle64, int64_t* buffer
 	hipIpcMemHandle_t h;
 	HC(hipIpcGetMemHandle(&h, nav->d_recv));
 	std::memcpy(handle64, &h, 64);
-	if (buffer_bytes) *buffer_bytes = (int64_t) (((size_t) nav->recvrecs * ((size_t) 8 + (size_t) MIX_REC * nav->cap) + PHD_MAX_DEVICES) * 8);
+	if (buffer_bytes) *buffer_bytes = (int64_t) (mig_recv_doubles(nav->recvrecs, nav->cap) * 8);
 	return PHD_OK;
 }
 
@@ -2329,9 +2348,8 @@ int phd_migration_push_async(phd_navigator* nav)
 		hipLaunchKernelGGL(k_pack_particles, dim3(std::min(nav->plan.sendcap, 256)), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (double*) nullptr,
 		                   (double* const*) nav->d_recv_tab);
 		if (nav->landing_flags && nav->world > 1) {
-			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
 			hipLaunchKernelGGL(k_post_landing, dim3(1), dim3(64), 0, nav->stream, (double* const*) nav->d_recv_tab, nav->world, nav->rank,
-			                   (size_t) nav->recvrecs * rec, nav->landing_seq);
+			                   mig_landing_offset(nav->recvrecs, nav->cap), nav->landing_seq);
 		}
 	}
 	HC(hipGetLastError());
@@ -2423,11 +2441,11 @@ int phd_test_migration_plan(phd_navigator* nav, const int32_t* gsrc, int particl
 		if (rc) return rc;
 		e = hipStreamSynchronize(nav->stream);
 	}
-	std::vector<int> c(2 * n + 4);
+	std::vector<int> c(mig_word(n, MC_DEVICE_WORDS));
 	if (e == hipSuccess) e = hipMemcpy(c.data(), nav->plan.counts, c.size() * 4, hipMemcpyDeviceToHost);
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_migration_plan: ") + hipGetErrorString(e));
 	for (int r = 0; r < n; r++) { send_counts[r] = c[r]; recv_counts[r] = c[n + r]; }
-	*nsend = c[2 * n]; *nrecv = c[2 * n + 1]; *status = c[2 * n + 2];
+	*nsend = c[mig_word(n, MC_NSEND)]; *nrecv = c[mig_word(n, MC_NRECV)]; *status = c[mig_word(n, MC_STATUS)];
 	if (*status == MIG_OK && resampled) {
 		std::vector<long long> sd((size_t) std::max(*nsend, 1));
 		HC(hipMemcpy(dst_code, nav->plan.code, (size_t) Pl * 4, hipMemcpyDeviceToHost));
@@ -2454,30 +2472,30 @@ int phd_migration_plan(phd_navigator* nav, int rank, int world_size, int32_t* se
 	const int n = world_size;
 	volatile int* hc = nav->h_counts;
 	const auto t0 = std::chrono::steady_clock::now();
-	for (long spins = 0; hc[2 * n + 6] != nav->plan_seq; spins++) {
+	for (long spins = 0; hc[mig_word(n, MC_SEQ)] != nav->plan_seq; spins++) {
 		__builtin_ia32_pause();
 		if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
 			// (a device that never gets there: report what the stream says rather than spin for ever)
 			HC(hipStreamSynchronize(nav->stream));
-			if (hc[2 * n + 6] != nav->plan_seq) return nav->fail(PHD_ERR_DEVICE, "phd_migration_plan: the plan kernel did not report");
+			if (hc[mig_word(n, MC_SEQ)] != nav->plan_seq) return nav->fail(PHD_ERR_DEVICE, "phd_migration_plan: the plan kernel did not report");
 		}
 	}
 	__atomic_thread_fence(__ATOMIC_ACQUIRE);
 	nav->plan_waiting = false;
-	const int status = hc[2 * n + 2];
+	const int status = hc[mig_word(n, MC_STATUS)];
 	for (int r = 0; r < n; r++) { send_counts[r] = hc[r]; recv_counts[r] = hc[n + r]; }
-	nav->nsend = hc[2 * n]; nav->nrecv = hc[2 * n + 1];
+	nav->nsend = hc[mig_word(n, MC_NSEND)]; nav->nrecv = hc[mig_word(n, MC_NRECV)];
 	if (status == MIG_DROPPED) {
 		// a kernel of the local step raised a flag: the step is dropped before anything rotates (the caller must not go on to
 		// pack / unpack — if it does, those kernels find the same status and leave the state alone; the state is the one
 		// before phd_step_local_async)
-		nav->h_flags = hc[2 * n + 5];
+		nav->h_flags = hc[mig_word(n, MC_FLAGS)];
 		hipMemsetAsync(nav->d_flags, 0, 4, nav->stream);
 		return check_flags(nav);
 	}
 	if (status == MIG_BAD) return nav->fail(PHD_ERR_GENERIC, "phd_migration_plan: the gathered source vector is not a resampling result (were the weights of all ranks gathered?)");
 	if (status == MIG_OVERFLOW) return nav->fail(PHD_ERR_CAPACITY, "phd_migration_plan: more migrating particles than the send list holds");
-	nav->h_info[0] = hc[2 * n + 4]; nav->h_info[1] = hc[2 * n + 3];
+	nav->h_info[0] = hc[mig_word(n, MC_BEST)]; nav->h_info[1] = hc[mig_word(n, MC_RESAMPLED)];
 	return PHD_OK;
 }
 
@@ -2492,7 +2510,7 @@ int phd_last_resampled(phd_navigator* nav)
 void* phd_migration_send_buffer(phd_navigator* nav, int64_t* bytes_per_particle)
 {
 	if (!nav || nav->multi || ensure_sharded(nav)) return nullptr;
-	if (bytes_per_particle) *bytes_per_particle = (int64_t) ((size_t) 8 + (size_t) 10 * nav->cap) * 8;
+	if (bytes_per_particle) *bytes_per_particle = (int64_t) mig_rec_doubles(nav->cap) * 8;
 	return nav->d_send;   // (a fixed address for the life of the handle)
 }
 
@@ -2525,8 +2543,7 @@ static int step_finish(phd_navigator* nav)
 	{
 		Timed t(nav, T_GR, nav->stream);
 		if (nav->landing_flags && nav->plan_on_device && nav->world > 1) {   // one wave waits, in front of the launch that reads
-			const size_t rec = (size_t) 8 + (size_t) MIX_REC * nav->cap;
-			const unsigned long long* landing = (const unsigned long long*) (nav->d_recv + (size_t) nav->recvrecs * rec);
+			const unsigned long long* landing = (const unsigned long long*) (nav->d_recv + mig_landing_offset(nav->recvrecs, nav->cap));
 			hipLaunchKernelGGL(k_wait_landing, dim3(1), dim3(64), 0, nav->stream, nav->plan, nav->world, landing, nav->landing_seq, nav->landing_ticks, nav->d_flags);
 		}
 		hipLaunchKernelGGL(k_finish_sharded, dim3(nav->P), dim3(256), 0, nav->stream, b, nav->plan, nav->world, (const double*) nav->d_recv,
