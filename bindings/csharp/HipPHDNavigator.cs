@@ -58,6 +58,11 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_history_enable(HandleRef nav, int capacity);
 	[DllImport(Lib)] public extern static int    phd_history_append(HandleRef nav, double time);
 	[DllImport(Lib)] public extern static int    phd_trajectories(HandleRef nav, int[] particles, int nparticles, out int length, out IntPtr times, out IntPtr poses7, out IntPtr slots);
+	[DllImport(Lib)] public extern static int    phd_trajectories_at(HandleRef nav, int entry, int[] slots, int nslots, out int length, out IntPtr times, out IntPtr poses7, out IntPtr outslots);
+	[DllImport(Lib)] public extern static int    phd_map_history_enable(HandleRef nav, int entries, long components);
+	[DllImport(Lib)] public extern static int    phd_map_history_append(HandleRef nav, double time);
+	[DllImport(Lib)] public extern static int    phd_map_history(HandleRef nav, out int length, out IntPtr times, out IntPtr best, out IntPtr bestpose7, out IntPtr counts, out IntPtr offsets,
+	                                                              out IntPtr w, out IntPtr mean3, out IntPtr cov9);
 }
 
 /// <summary>
@@ -208,6 +213,22 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 	{
 		int length; IntPtr times, poses, slots;
 		Check(PhdHipLib.phd_trajectories(nav, new int[] {particle}, 1, out length, out times, out poses, out slots));
+		return ToWay(length, times, poses);
+	}
+
+	/// <summary>DeviceWayPoints as it was at trajectory-log entry `entry`, for the particle that held `slot` then: entry + 1
+	/// entries, nothing that resampled later enters (phd_trajectories_at; waits for the device). A host that posted its frames
+	/// without waiting rebuilds UpdateTrajectory's copies from this: the best particle at the Update of a frame is the Best of
+	/// the newest DeviceWayMaps entry before it, or 0 after a reset.</summary>
+	public List<Tuple<double, double[]>> DeviceWayPointsAt(int entry, int slot)
+	{
+		int length; IntPtr times, poses, slots;
+		Check(PhdHipLib.phd_trajectories_at(nav, entry, new int[] {slot}, 1, out length, out times, out poses, out slots));
+		return ToWay(length, times, poses);
+	}
+
+	static List<Tuple<double, double[]>> ToWay(int length, IntPtr times, IntPtr poses)
+	{
 		double[] t = new double[length], x = new double[7 * length];
 		if (length > 0) { Marshal.Copy(times, t, 0, length); Marshal.Copy(poses, x, 0, 7 * length); }
 		var way = new List<Tuple<double, double[]>>(length);               // TimedState
@@ -217,6 +238,53 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 			way.Add(Tuple.Create(t[k], state));
 		}
 		return way;
+	}
+
+	/// <summary>True while the device keeps the best map of every frame (EnableDeviceMapHistory).</summary>
+	public bool DeviceMapHistory { get; private set; }
+
+	/// <summary>The map log on the device (phd_map_history_enable): room for `entries` frames and `components` components over all
+	/// of them, entries = 0 switches it off. Every call restarts it, as does every reset. Single-device handles only.</summary>
+	public void EnableDeviceMapHistory(int entries, long components)
+	{
+		Check(PhdHipLib.phd_map_history_enable(nav, entries, components));
+		DeviceMapHistory = entries > 0;
+	}
+
+	/// <summary>One entry of the map log: the best particle's map, slot and pose as they are behind everything posted so far
+	/// (phd_map_history_append; asynchronous: correct right behind phd_step_async). ≙ UpdateMapHistory (Navigator.cs:269-272)
+	/// for a host that does not wait for its steps.</summary>
+	public void AppendDeviceMapHistory(GameTime time)
+	{
+		Check(PhdHipLib.phd_map_history_append(nav, time.TotalGameTime.TotalSeconds));
+	}
+
+	/// <summary>≙ WayMaps (Navigator.cs:269-272) as the device kept it, with the best particle and its pose beside every map,
+	/// oldest entry first (phd_map_history; waits for the device).</summary>
+	public List<Tuple<double, int, double[], Map>> DeviceWayMaps()
+	{
+		int length; IntPtr times, best, poses, counts, offsets, w, m, c;
+		Check(PhdHipLib.phd_map_history(nav, out length, out times, out best, out poses, out counts, out offsets, out w, out m, out c));
+		double[] t = new double[length], x = new double[7 * length];
+		int[]    b = new int[length], n = new int[length];
+		long[]   off = new long[length + 1];
+		Marshal.Copy(offsets, off, 0, length + 1);
+		if (length > 0) { Marshal.Copy(times, t, 0, length); Marshal.Copy(poses, x, 0, 7 * length); Marshal.Copy(best, b, 0, length); Marshal.Copy(counts, n, 0, length); }
+		int      total = (int) off[length];
+		double[] ws = new double[total], ms = new double[3 * total], cs = new double[9 * total];
+		if (total > 0) { Marshal.Copy(w, ws, 0, total); Marshal.Copy(m, ms, 0, 3 * total); Marshal.Copy(c, cs, 0, 9 * total); }
+		var maps = new List<Tuple<double, int, double[], Map>>(length);
+		for (int k = 0; k < length; k++) {
+			Map map = new Map(3);
+			for (long i = off[k]; i < off[k] + n[k]; i++) {
+				double[][] cov = { new double[] {cs[9*i], cs[9*i+1], cs[9*i+2]}, new double[] {cs[9*i+3], cs[9*i+4], cs[9*i+5]}, new double[] {cs[9*i+6], cs[9*i+7], cs[9*i+8]} };
+				map.Add(new Gaussian(new double[] {ms[3*i], ms[3*i+1], ms[3*i+2]}, cov, ws[i]));
+			}
+			double[] state = new double[7];
+			Array.Copy(x, 7 * k, state, 0, 7);
+			maps.Add(Tuple.Create(t[k], b[k], state, map));
+		}
+		return maps;
 	}
 
 	/// <summary>≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531) for a batch of
@@ -275,6 +343,7 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 			VehicleParticles = particles;
 		}
 		UpdateMapHistory(time);
+		if (DeviceMapHistory) { AppendDeviceMapHistory(time); }
 	}
 
 	protected override void StartSlamInternal()    { Collapse(ParticleCount); }

@@ -273,6 +273,48 @@ int phd_history_enable(phd_navigator* nav, int capacity);
 int phd_history_append(phd_navigator* nav, double time);
 int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticles, int* length,
                      const double** times, const double** poses7, const int32_t** slots);
+/* phd_trajectories_at the paths, up to trajectory-log entry `entry`, of the particles that held `slots[i]` AT that entry:
+ *                     shape and conventions are phd_trajectories', *length = entry + 1, and nothing that resampled after the
+ *                     entry enters (≙ a copy of WayPoints taken at that frame, as UpdateTrajectory takes one of the best
+ *                     particle's: Navigator.cs:258-262). PHD_ERR_BAD_ARGUMENT on a multi-device handle, with the log off,
+ *                     for an entry outside [0, length) and for a slot outside [0, particles). Which particle was best at
+ *                     that frame is the `best` of the newest map-log entry (below) made before it, or 0 after a reset:
+ *                     BestParticle changes in SlamUpdate and reset alone.                                                */
+int phd_trajectories_at(phd_navigator* nav, int entry, const int32_t* slots, int nslots, int* length,
+                        const double** times, const double** poses7, const int32_t** out_slots);
+
+/* ---- the best map of every frame on the device (Navigator.WayMaps: UpdateMapHistory, Navigator.cs:269-272, at the end of
+ * every SlamUpdate, PHDNavigator.cs:361; what maps.out is written from) ----------------------------------------------------
+ * An opt-in log per handle of BestMapModel, written on the handle's stream without a host wait: an append stores the best
+ * particle's components, their number, BestParticle and its pose as they are behind everything enqueued before it. Which
+ * particle is best, where its map lies and how large it is are looked up on the device; the host keeps only `time`. A dropped
+ * step changes nothing: the append behind it logs the state before it, which is what the getters report. Off (the default)
+ * nothing is launched for it. Independent of the trajectory log: either may be on without the other.
+ *
+ * phd_map_history_enable  room for `entries` appends and for `components` components in all (80 bytes each; the sum of the
+ *                         logged maps' sizes). entries = 0 switches the log off and frees it; a negative number is
+ *                         PHD_ERR_BAD_ARGUMENT. Every call restarts the log at length 0 and waits for the handle's streams.
+ *                         A failed allocation is PHD_ERR_DEVICE and leaves the log off. Refused with PHD_ERR_BAD_ARGUMENT
+ *                         on a multi-device handle and on one that has run sharded steps; while the log is on,
+ *                         phd_step_local_async and phd_step_global[_device]_async are refused the same way (the best
+ *                         particle may live on another shard).
+ * phd_map_history_append  one entry. Asynchronous like phd_history_append (one launch on the handle's stream): correct right
+ *                         behind phd_step_async. An entry whose components do not fit what is left of `components` stores
+ *                         none and gets the count -1; later entries that fit are stored. A log of `entries` entries:
+ *                         PHD_ERR_CAPACITY at once, nothing is enqueued and the log is as it was. A log that is off, a
+ *                         handle without particles and frozen mode (phd_set_frozen: BestParticle then describes a result
+ *                         the state never took): PHD_ERR_BAD_ARGUMENT.
+ * phd_map_history         the log, oldest entry first: *length entries; times, best, counts [length]; best_pose7
+ *                         [length][7]; offsets[length + 1], in components, into w / mean3 / cov9 (phd_map's conventions):
+ *                         entry k's components are offsets[k] .. offsets[k + 1]. Library-owned buffers, valid until the next
+ *                         call on the handle. Waits for the device; one copy of the entry table and one of the components
+ *                         in use. If an entry has the count -1 the call returns PHD_ERR_CAPACITY with all outputs set (that
+ *                         entry is empty); phd_last_error names the first one.
+ * phd_reset and phd_upload_state_soa restart the log (length 0, capacities kept).                                       */
+int phd_map_history_enable(phd_navigator* nav, int entries, int64_t components);
+int phd_map_history_append(phd_navigator* nav, double time);
+int phd_map_history(phd_navigator* nav, int* length, const double** times, const int32_t** best, const double** best_pose7,
+                    const int32_t** counts, const int64_t** offsets, const double** w, const double** mean3, const double** cov9);
 
 /* Stage-level entry points for the unit KATs (the stages behind PHDNavigator's public methods).
  *   phd_stage_run(z, with_alpha)  runs predict -> correct -> prune (-> alpha) on EVERY particle of the handle's state, without

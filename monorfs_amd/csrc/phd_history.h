@@ -63,6 +63,7 @@ __global__ __launch_bounds__(256) void k_hist_append(const StepBufs a, int P, do
 // particle; the entries newest to oldest in chunks of 64, lane l on entry hi - l. The ancestor slot `a` is one value per wave
 // and is chased (a = parent[k][a]) only at the entries a ballot of the dirty words names: the dependent trips to memory are as
 // many as the resampled entries, not as the path is long. Every lane then copies its own entry.
+// pend == NULL (phd_trajectories_at): the query names slots of entry L - 1 itself, no pending map lies before the first trip.
 __global__ __launch_bounds__(256) void k_hist_trace(const double* __restrict__ pose, const int* __restrict__ parent, const int* __restrict__ dirty,
                                                     const int* __restrict__ pend, const int* __restrict__ pdirty, const int* __restrict__ query,
                                                     int nq, int L, int P, int Ps, double* __restrict__ out_pose, int* __restrict__ out_slot)
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void k_hist_trace(const double* __restrict__ p
 	const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (q >= nq) return;   // (a whole wave)
 	const int p = hist_clamp(query[q], P);
-	int a = __builtin_amdgcn_readfirstlane(hist_clamp(*pdirty ? pend[p] : p, P));
+	int a = __builtin_amdgcn_readfirstlane(hist_clamp((pend && *pdirty) ? pend[p] : p, P));
 	for (int hi = L - 1; hi >= 0; hi -= 64) {
 		const int k = hi - lane;
 		// (entry 0 has no entry before it: whatever resampled before the first append composes nothing)

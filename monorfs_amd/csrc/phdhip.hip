@@ -6,8 +6,10 @@
 #include "../../include/phdhip.h"
 #include "phd_kernels.h"
 #include "phd_history.h"
+#include "phd_maplog.h"
 
 #include <algorithm>
+#include <cstdint>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -184,6 +186,12 @@ struct phd_navigator {
 	DevBuf<int> d_tq, d_tslot; DevBuf<double> d_tpose; PinBuf<int> h_tq, h_tslot; PinBuf<double> h_tpose; size_t tqcap = 0, tcap = 0;
 	int* hpend(int which) { return d_hpend + (size_t) which * Pcap; }
 	int* hpdirty(int which) { return d_hpend + 2 * (size_t) Pcap + which; }
+	// the map log (phd_map_history_enable; phd_maplog.h): mlog_cap entries over mlog_comps component records, mlog_len of them
+	// appended; mlog_pp: which copy of the bump word is current; the times stay on the host
+	int mlog_cap = 0, mlog_len = 0, mlog_pp = 0; long long mlog_comps = 0;
+	DevBuf<double> d_mlrec; DevBuf<MapLogEntry> d_mlentry; DevBuf<long long> d_mlbump;
+	std::vector<double> h_mltimes, h_mlrec, h_mlpose, h_mlw, h_mlm, h_mlc;
+	std::vector<MapLogEntry> h_mlentry; std::vector<int32_t> h_mlbest, h_mlcount; std::vector<int64_t> h_mloff;
 	// host mirrors handed out by the getters
 	std::vector<double> h_weights, h_poses, h_mw, h_mm, h_mc, h_alpha, h_setll, h_tmp;
 	std::vector<int32_t> h_src;
@@ -599,6 +607,15 @@ int check_flags(phd_navigator* nav)
 	return PHD_OK;
 }
 
+// a component record -> the ABI's w, mean[3], cov[9] (row-major, the full symmetric matrix)
+void unpack_record(const double* r, double* w, double* m, double* C)
+{
+	*w = r[0];
+	for (int k = 0; k < 3; k++) m[k] = r[1 + k];
+	const double xx = r[4], xy = r[5], xz = r[6], yy = r[7], yz = r[8], zz = r[9];
+	C[0] = xx; C[1] = xy; C[2] = xz; C[3] = xy; C[4] = yy; C[5] = yz; C[6] = xz; C[7] = yz; C[8] = zz;
+}
+
 // copy one particle's mixture into h_mw / h_mm / h_mc (row-major mean[3n], cov[9n]): its count from the bank of the small
 // arrays, its components from `mixbank` at the slot dslots[particle] (device array; NULL or the same bank: its own slot)
 int fetch_map(phd_navigator* nav, int bankidx, int particle, int* ncomp, int mixbank = -1, const int* dslots = nullptr)
@@ -622,14 +639,7 @@ int fetch_map(phd_navigator* nav, int bankidx, int particle, int* ncomp, int mix
 	nav->h_mm.resize((size_t) 3 * std::max(n, 1));
 	nav->h_mc.resize((size_t) 9 * std::max(n, 1));
 	const double* t = nav->h_tmp.data();
-	for (int c = 0; c < n; c++) {
-		const double* r = t + (size_t) c * MIX_REC;
-		nav->h_mw[c] = r[0];
-		for (int k = 0; k < 3; k++) nav->h_mm[c * 3 + k] = r[1 + k];
-		double xx = r[4], xy = r[5], xz = r[6], yy = r[7], yz = r[8], zz = r[9];
-		double* C = &nav->h_mc[(size_t) c * 9];
-		C[0] = xx; C[1] = xy; C[2] = xz; C[3] = xy; C[4] = yy; C[5] = yz; C[6] = xz; C[7] = yz; C[8] = zz;
-	}
+	for (int c = 0; c < n; c++) unpack_record(t + (size_t) c * MIX_REC, &nav->h_mw[c], &nav->h_mm[(size_t) c * 3], &nav->h_mc[(size_t) c * 9]);
 	*ncomp = n;
 	return PHD_OK;
 }
@@ -717,6 +727,23 @@ int hist_restart(phd_navigator* nav)
 	return PHD_OK;
 }
 
+// The map log starts again: no entries, no records used (on the handle's stream, behind whatever still reads it).
+int mlog_restart(phd_navigator* nav)
+{
+	nav->mlog_len = 0;
+	nav->h_mltimes.clear();
+	if (nav->mlog_cap < 1) return PHD_OK;
+	HC(hipMemsetAsync(nav->d_mlbump, 0, 2 * sizeof(long long), nav->stream));
+	return PHD_OK;
+}
+
+// ... both logs (phd_reset, phd_upload_state_soa)
+int logs_restart(phd_navigator* nav)
+{
+	const int rc = hist_restart(nav);
+	return rc ? rc : mlog_restart(nav);
+}
+
 // Behind the end of a step, on the stream that ran it: the step's resampling (if it had one and was not dropped) goes into pend.
 int hist_compose(phd_navigator* nav, hipStream_t st)
 {
@@ -751,7 +778,9 @@ void multi_destroy(phd_navigator* nav);
 phd_navigator* multi_shard0(phd_navigator* nav);
 static void multi_timing_reset(phd_navigator* nav, uint8_t enabled);
 #define MULTI_UNSUPPORTED(nav, what) if ((nav) && (nav)->multi) return (nav)->fail(PHD_ERR_BAD_ARGUMENT, what ": not available on a multi-device handle (use a single-device handle)")
-#define HISTORY_UNSUPPORTED(nav, what) if ((nav) && (nav)->hist_cap > 0) return (nav)->fail(PHD_ERR_BAD_ARGUMENT, what ": not available while the trajectory log is on (phd_history_enable(nav, 0) switches it off; sharded ancestry is not kept)")
+#define HISTORY_UNSUPPORTED(nav, what) if ((nav) && ((nav)->hist_cap > 0 || (nav)->mlog_cap > 0)) return (nav)->fail(PHD_ERR_BAD_ARGUMENT, (nav)->hist_cap > 0 ? \
+	what ": not available while the trajectory log is on (phd_history_enable(nav, 0) switches it off; sharded ancestry is not kept)" : \
+	what ": not available while the map log is on (phd_map_history_enable(nav, 0, 0) switches it off; the best particle may live on another shard)")
 
 // =================================================================================================
 extern "C" {
@@ -1029,7 +1058,7 @@ static int reset_impl(phd_navigator* nav, int nparticles, const double* pose7, c
 	nav->h_info[0] = 0; nav->h_info[1] = 0;   // BestParticle = 0 (:265)
 	HC(hipMemcpy(nav->d_info, nav->h_info, 8, hipMemcpyHostToDevice));
 	nav->stage_valid = false;
-	return hist_restart(nav);
+	return logs_restart(nav);
 }
 
 int phd_reset(phd_navigator* nav, int nparticles, const double* pose7, const double* w, const double* mean3,
@@ -1265,7 +1294,7 @@ static int upload_impl(phd_navigator* nav, int nparticles, int stride, const dou
 	HC(hipMemcpy(nav->bank[I].weights, weights, (size_t) nparticles * 8, hipMemcpyHostToDevice));
 	nav->P = nparticles;
 	nav->stage_valid = false;
-	return hist_restart(nav);
+	return logs_restart(nav);
 }
 
 int phd_upload_state_soa(phd_navigator* nav, int nparticles, int stride, const double* planes, const int32_t* counts,
@@ -1660,17 +1689,19 @@ int phd_history_append(phd_navigator* nav, double time)
 	return PHD_OK;
 }
 
-int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticles, int* length, const double** times, const double** poses7, const int32_t** slots)
+// phd_trajectories (entry < 0: the particles of the current state, through the pending map) and phd_trajectories_at (the
+// particles that held the slots at `entry`: the log's first entry + 1 rows, no pending map). `what`: how `who` calls its list.
+static int trajectories(phd_navigator* nav, const char* who, const char* what, int entry, const int32_t* particles, int nparticles, int* length, const double** times,
+                        const double** poses7, const int32_t** slots)
 {
-	if (!nav) return PHD_ERR_BAD_ARGUMENT;
-	MULTI_UNSUPPORTED(nav, "phd_trajectories");
-	if (nav->hist_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories: the trajectory log is off (phd_history_enable)");
-	if (!particles || nparticles < 1 || !length) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories: a list of at least one particle and `length`");
+	if (nav->hist_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, std::string(who) + ": the trajectory log is off (phd_history_enable)");
+	if (!particles || nparticles < 1 || !length) return nav->fail(PHD_ERR_BAD_ARGUMENT, std::string(who) + ": a list of at least one " + what + " and `length`");
+	if (entry >= nav->hist_len) return nav->fail(PHD_ERR_BAD_ARGUMENT, std::string(who) + ": entry " + std::to_string(entry) + " of " + std::to_string(nav->hist_len));
 	for (int i = 0; i < nparticles; i++) {
-		if (particles[i] < 0 || particles[i] >= nav->P) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories: particle " + std::to_string(particles[i]) + " out of range");
+		if (particles[i] < 0 || particles[i] >= nav->P) return nav->fail(PHD_ERR_BAD_ARGUMENT, std::string(who) + ": " + what + " " + std::to_string(particles[i]) + " out of range");
 	}
 	enter(nav);
-	const int L = nav->hist_len;
+	const int L = entry < 0 ? nav->hist_len : entry + 1;
 	const size_t cells = std::max((size_t) nparticles * L, (size_t) 1);
 	if ((size_t) nparticles > nav->tqcap) {
 		nav->tqcap = 0;
@@ -1693,7 +1724,8 @@ int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticle
 		HC(hipMemcpyAsync(nav->d_tq, nav->h_tq, (size_t) nparticles * 4, hipMemcpyHostToDevice, nav->stream));
 		const int o = nav->hist_pp;
 		hipLaunchKernelGGL(k_hist_trace, dim3((nparticles + 3) / 4), dim3(256), 0, nav->stream, (const double*) nav->d_hpose, (const int*) nav->d_hparent, (const int*) nav->d_hdirty,
-		                   (const int*) nav->hpend(o), (const int*) nav->hpdirty(o), (const int*) nav->d_tq, nparticles, L, nav->P, nav->Pcap, (double*) nav->d_tpose, (int*) nav->d_tslot);
+		                   entry < 0 ? (const int*) nav->hpend(o) : nullptr, (const int*) nav->hpdirty(o), (const int*) nav->d_tq, nparticles, L, nav->P, nav->Pcap,
+		                   (double*) nav->d_tpose, (int*) nav->d_tslot);
 		HC(hipGetLastError());
 		HC(hipMemcpyAsync(nav->h_tpose, nav->d_tpose, (size_t) nparticles * L * 7 * 8, hipMemcpyDeviceToHost, nav->stream));
 		HC(hipMemcpyAsync(nav->h_tslot, nav->d_tslot, (size_t) nparticles * L * 4, hipMemcpyDeviceToHost, nav->stream));
@@ -1703,6 +1735,116 @@ int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticle
 	if (times) *times = nav->h_htimes.data();
 	if (poses7) *poses7 = nav->h_tpose;
 	if (slots) *slots = nav->h_tslot;
+	return PHD_OK;
+}
+
+int phd_trajectories(phd_navigator* nav, const int32_t* particles, int nparticles, int* length, const double** times, const double** poses7, const int32_t** slots)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_trajectories");
+	return trajectories(nav, "phd_trajectories", "particle", -1, particles, nparticles, length, times, poses7, slots);
+}
+
+int phd_trajectories_at(phd_navigator* nav, int entry, const int32_t* slots, int nslots, int* length, const double** times, const double** poses7, const int32_t** out_slots)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_trajectories_at");
+	if (entry < 0) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_trajectories_at: entry " + std::to_string(entry) + " (entries count from 0)");
+	return trajectories(nav, "phd_trajectories_at", "slot", entry, slots, nslots, length, times, poses7, out_slots);
+}
+
+// ---- the map log (phd_maplog.h) -------------------------------------------------------------------
+int phd_map_history_enable(phd_navigator* nav, int entries, int64_t components)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_map_history_enable");
+	if (entries < 0 || components < 0) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history_enable: entries and components are counts, entries = 0 switches the log off");
+	if (nav->sharded_used) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history_enable: this handle runs sharded steps (the best particle may live on another shard)");
+	// (the byte count of the records must fit a size_t: the kernel's bound is `components`, the buffer must be that large)
+	if ((uint64_t) components > SIZE_MAX / (MIX_REC * sizeof(double))) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history_enable: components beyond what can be addressed");
+	enter(nav);
+	// (kernels of posted steps and appends may still write the buffers that go)
+	HC(hipStreamSynchronize(nav->stream));
+	for (int s = 0; s < phd_navigator::MAXSPLIT - 1; s++) if (nav->aux[s]) HC(hipStreamSynchronize(nav->aux[s]));
+	nav->mlog_cap = 0; nav->mlog_len = 0; nav->mlog_comps = 0; nav->h_mltimes.clear();
+	nav->d_mlrec.reset(); nav->d_mlentry.reset(); nav->d_mlbump.reset();
+	if (entries == 0) return PHD_OK;
+	hipError_t e = nav->d_mlrec.alloc((size_t) std::max<int64_t>(components, 1) * MIX_REC);
+	if (e == hipSuccess) e = nav->d_mlentry.alloc(entries);
+	if (e == hipSuccess) e = nav->d_mlbump.alloc(2);
+	if (e != hipSuccess) {
+		(void) hipGetLastError();
+		nav->d_mlrec.reset(); nav->d_mlentry.reset(); nav->d_mlbump.reset();
+		return nav->fail(PHD_ERR_DEVICE, std::string("phd_map_history_enable: ") + std::to_string((long long) components) + " components of 80 bytes and " + std::to_string(entries) +
+		                 " entries for the log: " + hipGetErrorString(e));
+	}
+	nav->mlog_cap = entries;
+	nav->mlog_comps = components;
+	nav->mlog_pp = 0;
+	return mlog_restart(nav);
+}
+
+int phd_map_history_append(phd_navigator* nav, double time)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_map_history_append");
+	if (nav->mlog_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history_append: the map log is off (phd_map_history_enable)");
+	if (nav->P < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history_append: no particles (call phd_reset first)");
+	if (nav->frozen) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history_append: frozen mode (the best particle describes a result the state never took)");
+	if (nav->mlog_len >= nav->mlog_cap) return nav->fail(PHD_ERR_CAPACITY, "phd_map_history_append: the map log is full (" + std::to_string(nav->mlog_cap) + " entries)");
+	enter(nav);
+	const int k = nav->mlog_len, o = nav->mlog_pp, n = o ^ 1;
+	StepBufs b = make_bufs(nav);
+	hipLaunchKernelGGL((k_maplog_append<MapLogEntry>), dim3((nav->cap * (MIX_REC / 2) + 255) / 256), dim3(256), 0, nav->stream, b, (const int*) nav->d_info, nav->P, nav->Pcap, (double*) nav->d_mlrec,
+	                   (long long) nav->mlog_comps, nav->d_mlentry + k, (const long long*) (nav->d_mlbump + o), nav->d_mlbump + n);
+	HC(hipGetLastError());
+	nav->mlog_pp = n;
+	nav->mlog_len = k + 1;
+	nav->h_mltimes.push_back(time);
+	return PHD_OK;
+}
+
+int phd_map_history(phd_navigator* nav, int* length, const double** times, const int32_t** best, const double** best_pose7, const int32_t** counts, const int64_t** offsets,
+                    const double** w, const double** mean3, const double** cov9)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_map_history");
+	if (nav->mlog_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history: the map log is off (phd_map_history_enable)");
+	if (!length) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_history: `length`");
+	enter(nav);
+	const int L = nav->mlog_len;
+	nav->h_mlentry.resize(std::max(L, 1));
+	if (L > 0) HC(hipMemcpyAsync(nav->h_mlentry.data(), nav->d_mlentry, (size_t) L * sizeof(MapLogEntry), hipMemcpyDeviceToHost, nav->stream));
+	HC(hipStreamSynchronize(nav->stream));
+	nav->h_mlbest.resize(std::max(L, 1)); nav->h_mlcount.resize(std::max(L, 1)); nav->h_mloff.assign((size_t) L + 1, 0); nav->h_mlpose.resize((size_t) std::max(L, 1) * 7);
+	int64_t used = 0;
+	int firstbad = -1;
+	for (int k = 0; k < L; k++) {
+		const MapLogEntry& e = nav->h_mlentry[k];
+		const int c = e.count;
+		if (e.offset != used || c < -1 || c > nav->cap || used + std::max(c, 0) > nav->mlog_comps) return nav->fail(PHD_ERR_GENERIC, "phd_map_history: corrupt entry " + std::to_string(k));
+		if (c < 0 && firstbad < 0) firstbad = k;
+		nav->h_mlbest[k] = e.best; nav->h_mlcount[k] = c; nav->h_mloff[k] = used;
+		std::memcpy(&nav->h_mlpose[(size_t) k * 7], e.pose, 7 * 8);
+		used += std::max(c, 0);
+	}
+	nav->h_mloff[L] = used;
+	const size_t n = (size_t) used;
+	nav->h_mlrec.resize(std::max(n, (size_t) 1) * MIX_REC);
+	if (n > 0) HC(hipMemcpy(nav->h_mlrec.data(), nav->d_mlrec, n * MIX_REC * 8, hipMemcpyDeviceToHost));
+	nav->h_mlw.resize(std::max(n, (size_t) 1)); nav->h_mlm.resize(std::max(n, (size_t) 1) * 3); nav->h_mlc.resize(std::max(n, (size_t) 1) * 9);
+	for (size_t c = 0; c < n; c++) unpack_record(nav->h_mlrec.data() + c * MIX_REC, &nav->h_mlw[c], &nav->h_mlm[c * 3], &nav->h_mlc[c * 9]);
+	*length = L;
+	if (times) *times = nav->h_mltimes.data();
+	if (best) *best = nav->h_mlbest.data();
+	if (best_pose7) *best_pose7 = nav->h_mlpose.data();
+	if (counts) *counts = nav->h_mlcount.data();
+	if (offsets) *offsets = nav->h_mloff.data();
+	if (w) *w = nav->h_mlw.data();
+	if (mean3) *mean3 = nav->h_mlm.data();
+	if (cov9) *cov9 = nav->h_mlc.data();
+	if (firstbad >= 0) return nav->fail(PHD_ERR_CAPACITY, "phd_map_history: entry " + std::to_string(firstbad) + " did not fit the log's " + std::to_string(nav->mlog_comps) +
+	                                    " components and holds no records (count -1)");
 	return PHD_OK;
 }
 

@@ -110,16 +110,52 @@ public:
 		const double *t = nullptr, *x = nullptr;
 		const int32_t* s = nullptr;
 		check(phd_trajectories(nav_, particles.data(), (int) particles.size(), &L, &t, &x, &s));
-		Trajectories out;
-		out.Times.assign(t, t + (L > 0 ? L : 0));
-		out.Poses.assign(particles.size(), std::vector<Pose3D>(L));
-		out.Slots.assign(particles.size(), std::vector<int32_t>(L));
-		for (size_t j = 0; j < particles.size(); j++) {
-			for (int k = 0; k < L; k++) {
-				const double* q = x + (j * L + k) * 7;
-				std::copy(q, q + 7, out.Poses[j][k].begin());
-				out.Slots[j][k] = s[j * L + k];
-			}
+		return trajectories(particles.size(), L, t, x, s);
+	}
+
+	// WayPoints as they were at trajectory-log entry `entry`, of the particles that held `slots` then: entry + 1 entries, nothing
+	// that resampled later enters (phd_trajectories_at; waits for the device)
+	Trajectories WayPointsAt(int entry, const std::vector<int32_t>& slots)
+	{
+		int L = 0;
+		const double *t = nullptr, *x = nullptr;
+		const int32_t* s = nullptr;
+		check(phd_trajectories_at(nav_, entry, slots.data(), (int) slots.size(), &L, &t, &x, &s));
+		return trajectories(slots.size(), L, t, x, s);
+	}
+
+	// The best map of every frame on the device (phd_map_history_enable; Navigator.WayMaps): room for `entries` entries and
+	// `components` components over all of them, entries = 0 switches the log off; every call restarts it
+	void enableMapHistory(int entries, int64_t components)
+	{
+		check(phd_map_history_enable(nav_, entries, components));
+		maphistory_ = entries > 0;
+	}
+
+	// one entry: the best particle's map, slot and pose (phd_map_history_append; asynchronous)
+	void appendMapHistory(double time) { check(phd_map_history_append(nav_, time)); }
+
+	// ≙ Navigator.WayMaps (Navigator.cs:269-272) with the best particle beside every map, oldest entry first (phd_map_history;
+	// waits for the device). An entry whose components did not fit the log throws (PHD_ERR_CAPACITY).
+	struct WayMap {
+		double  Time;
+		int32_t Best;
+		Pose3D  Pose;
+		Map     Model;
+	};
+	std::vector<WayMap> WayMaps()
+	{
+		int L = 0;
+		const double *t = nullptr, *x = nullptr, *w = nullptr, *m = nullptr, *c = nullptr;
+		const int32_t *b = nullptr, *n = nullptr;
+		const int64_t* off = nullptr;
+		check(phd_map_history(nav_, &L, &t, &b, &x, &n, &off, &w, &m, &c));
+		std::vector<WayMap> out(L);
+		for (int k = 0; k < L; k++) {
+			out[k].Time = t[k];
+			out[k].Best = b[k];
+			std::copy(x + k * 7, x + k * 7 + 7, out[k].Pose.begin());
+			out[k].Model = tomap(n[k], w + off[k], m + off[k] * 3, c + off[k] * 9);
 		}
 		return out;
 	}
@@ -162,6 +198,12 @@ public:
 	{
 		check(phd_slam_update(nav_, measurements.empty() ? nullptr : measurements[0].data(), (int) measurements.size(),
 		                      OnlyMapping ? 1 : 0, uniform));
+	}
+	// ... with the frame's time: the same, and the best map's entry when the map log is on (UpdateMapHistory, :361)
+	void SlamUpdate(double time, const std::vector<PixelRangeMeasurement>& measurements, double uniform)
+	{
+		SlamUpdate(measurements, uniform);
+		if (maphistory_) appendMapHistory(time);
 	}
 
 	std::vector<double> VehicleWeights()   // :128
@@ -251,6 +293,22 @@ private:
 		if (status != PHD_OK) throw PhdError(status, phd_last_error(nav_));
 	}
 
+	static Trajectories trajectories(size_t n, int L, const double* t, const double* x, const int32_t* s)
+	{
+		Trajectories out;
+		out.Times.assign(t, t + (L > 0 ? L : 0));
+		out.Poses.assign(n, std::vector<Pose3D>(L));
+		out.Slots.assign(n, std::vector<int32_t>(L));
+		for (size_t j = 0; j < n; j++) {
+			for (int k = 0; k < L; k++) {
+				const double* q = x + (j * L + k) * 7;
+				std::copy(q, q + 7, out.Poses[j][k].begin());
+				out.Slots[j][k] = s[j * L + k];
+			}
+		}
+		return out;
+	}
+
 	static Map tomap(int n, const double* w, const double* m, const double* c)
 	{
 		Map out(n);
@@ -276,6 +334,7 @@ private:
 
 	phd_navigator* nav_ = nullptr;
 	bool history_ = false;   // the trajectory log is on: UpdateOdometry(time, ...) appends
+	bool maphistory_ = false;   // the map log is on: SlamUpdate(time, ...) appends
 };
 
 }  // namespace monorfs

@@ -13,11 +13,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .abi import (PHD_ERR_ASSOCIATION, PHD_STAGE_CORRECTED, PHD_STAGE_PREDICTED, PHD_STAGE_PRUNED, PhdParams,
+from .abi import (PHD_ERR_ASSOCIATION, PHD_ERR_CAPACITY, PHD_STAGE_CORRECTED, PHD_STAGE_PREDICTED, PHD_STAGE_PRUNED, PhdParams,
                   prm3d_defaults)
 
 dp = _lib.dp
 ip = _lib.ip
+i64p = _lib.i64p
 
 
 def pose3d_add(pose7, delta6):
@@ -68,6 +69,7 @@ class PHDNavigator:
         if not self._h:
             raise PHDError(-1, self._lib.phd_create_error().decode())
         self._history, self._history_len = False, 0   # the trajectory log is on | its entries (the library's count, mirrored)
+        self._map_history, self._map_history_len = False, 0   # ... the map log
         self.ParticleCount = particlecount
         self.OnlyMapping = bool(onlymapping)
         n = 1 if onlymapping else particlecount   # :201-203
@@ -97,7 +99,7 @@ class PHDNavigator:
         w, m, c = (np.ascontiguousarray(x, np.float64) for x in model)
         pose = np.ascontiguousarray(pose, np.float64)
         self._check(self._lib.phd_reset(self._h, int(particlecount), _ptr(pose), _ptr(w), _ptr(m), _ptr(c), len(w)))
-        self._history_len = 0   # (the library restarts the log)
+        self._history_len = self._map_history_len = 0   # (the library restarts the logs)
 
     def CollapseParticles(self, particlecount):
         """≙ :233-236: every particle becomes a copy of the best one."""
@@ -139,7 +141,7 @@ class PHDNavigator:
         _, P, stride = planes.shape
         self._check(self._lib.phd_upload_state_soa(self._h, P, stride, _ptr(planes), counts.ctypes.data_as(ip),
                                                    _ptr(poses), _ptr(weights)))
-        self._history_len = 0
+        self._history_len = self._map_history_len = 0
 
     def download_state(self, stride):
         P = self.particle_count
@@ -213,6 +215,59 @@ class PHDNavigator:
         return (np.ctypeslib.as_array(t, shape=(L,)).copy(), np.ctypeslib.as_array(x, shape=(len(q) * L * 7,)).reshape(len(q), L, 7).copy(),
                 np.ctypeslib.as_array(s, shape=(len(q) * L,)).reshape(len(q), L).copy())
 
+    def WayPointsAt(self, entry, slots):
+        """WayPoints as they were at trajectory-log entry `entry`, for the particles that held `slots` then: entry + 1 entries,
+        nothing that resampled later enters (phd_trajectories_at; waits for the device)."""
+        q = np.ascontiguousarray(list(slots) if not isinstance(slots, np.ndarray) else slots, np.int32).reshape(-1)
+        n = C.c_int(0)
+        t, x, s = dp(), dp(), ip()
+        self._check(self._lib.phd_trajectories_at(self._h, int(entry), q.ctypes.data_as(ip), len(q), C.byref(n), C.byref(t), C.byref(x), C.byref(s)))
+        L = n.value
+        return (np.ctypeslib.as_array(t, shape=(L,)).copy(), np.ctypeslib.as_array(x, shape=(len(q) * L * 7,)).reshape(len(q), L, 7).copy(),
+                np.ctypeslib.as_array(s, shape=(len(q) * L,)).reshape(len(q), L).copy())
+
+    # ------------------------------------------------------------------ map history (Navigator.WayMaps)
+    def enable_map_history(self, entries, components):
+        """The map log on the device (phd_map_history_enable): room for `entries` entries, one per SlamUpdate with a time from
+        now on, and `components` components over all of them; entries = 0 switches it off. Every call restarts the log."""
+        self._check(self._lib.phd_map_history_enable(self._h, int(entries), int(components)))
+        self._map_history = int(entries) > 0
+        self._map_history_len = 0
+
+    def append_map_history(self, time=None):
+        """One entry of the log: the best particle's map, slot and pose (phd_map_history_append; asynchronous).
+        time=None: the entry's index."""
+        if time is None:
+            time = float(self.map_history_length)
+        self._check(self._lib.phd_map_history_append(self._h, float(time)))
+        self._map_history_len += 1
+
+    @property
+    def map_history_length(self):
+        return self._map_history_len if self._map_history else 0
+
+    def WayMaps(self, allow_missing=False):
+        """≙ Navigator.WayMaps (Navigator.cs:269-272) with the best particle beside every map: a list of
+        (time, best, pose[7], (w, mean, cov)), oldest entry first (phd_map_history; waits for the device). An entry whose
+        components did not fit the log raises PHDError (status 2); allow_missing=True returns the list with None as its map."""
+        n = C.c_int(0)
+        t, b, x, cnt, off, w, m, c = dp(), ip(), dp(), ip(), i64p(), dp(), dp(), dp()
+        rc = self._lib.phd_map_history(self._h, C.byref(n), C.byref(t), C.byref(b), C.byref(x), C.byref(cnt), C.byref(off), C.byref(w), C.byref(m), C.byref(c))
+        if rc != 0 and not (allow_missing and rc == PHD_ERR_CAPACITY and n.value > 0):
+            self._check(rc)
+        out = []
+        for k in range(n.value):
+            lo, k_n = off[k], cnt[k]
+            if k_n < 0:
+                model = None
+            elif k_n == 0:
+                model = (np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3, 3)))
+            else:
+                model = (np.ctypeslib.as_array(w, shape=(lo + k_n,))[lo:].copy(), np.ctypeslib.as_array(m, shape=((lo + k_n) * 3,))[lo * 3:].reshape(k_n, 3).copy(),
+                         np.ctypeslib.as_array(c, shape=((lo + k_n) * 9,))[lo * 9:].reshape(k_n, 3, 3).copy())
+            out.append((t[k], b[k], np.array(x[k * 7:k * 7 + 7]), model))
+        return out
+
     def QuasiSetLogLikelihood(self, measurements, landmarks, poses):
         """≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531), batched over
         candidate poses (phd_quasi_set_loglik): returns one value per pose."""
@@ -275,9 +330,12 @@ class PHDNavigator:
         return out
 
     def SlamUpdate(self, time, measurements, u_resample=0.5):
-        """≙ PHDNavigator.SlamUpdate (:323-362)."""
+        """≙ PHDNavigator.SlamUpdate (:323-362). With the map log on and a time given, the step's best map is appended behind it
+        (UpdateMapHistory, :361)."""
         z = np.ascontiguousarray(measurements, np.float64).reshape(-1, 3)
         self._check(self._lib.phd_slam_update(self._h, _ptr(z), len(z), int(self.OnlyMapping), float(u_resample)))
+        if self._map_history and time is not None:
+            self.append_map_history(time)
 
     @property
     def VehicleWeights(self):

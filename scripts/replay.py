@@ -3,7 +3,7 @@
 drives the C# solver with `-i=record` drives PHDNavigator here, and estimate.out / maps.out come back in the same
 format (Simulation.SaveToFile, Simulation.cs:391-488).
 
-    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints]
+    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints] [--posted]
     python scripts/replay.py --make DIR [--frames K]      # write a small synthetic record first
 
 The host keeps what the reference keeps managed: the motion noise dt * chol(Q) * N(0, I) per particle and the
@@ -12,7 +12,11 @@ resampling uniform are drawn here (numpy), the motion step itself runs on the de
 estimate.out: with --estimate poses (the default) every frame's trajectory is the list of the best poses of the frames so
 far; with --estimate waypoints it is what the reference writes, the best particle's own path (BestEstimate.WayPoints,
 copied by Navigator.UpdateTrajectory, Navigator.cs:258-262), read from the trajectory log on the device
-(phd_history_enable / phd_trajectories). The two differ whenever a step resamples or the best particle changes."""
+(phd_history_enable / phd_trajectories). The two differ whenever a step resamples or the best particle changes.
+
+--posted: the whole record is posted to the device without a host wait between the first frame and the last (phd_step_async,
+the map log phd_map_history_* and, for waypoints, the trajectory log); the two files are built afterwards from the logs and are
+the same bytes."""
 import argparse
 import os
 import sys
@@ -73,8 +77,34 @@ class DeviceSolver:
             self.nav.SlamUpdate(time, z, u_resample=u)
         return (times, poses[0]), self.nav.MapModel(self.nav.BestParticle)
 
+    def start_posted(self, frames, components):
+        """the map log (Navigator.WayMaps): one entry per frame"""
+        self.nav.enable_map_history(frames, components)
 
-def replay(rec, particles, seed, solver_cls, estimate="poses"):
+    def post(self, time, reading, noise, z, u):
+        """a frame with no getter and no wait: the motion step (and its waypoint if the trajectory log is on), the step if the
+        frame has measurements, the best map behind it"""
+        self.nav.UpdateOdometry(time, reading, noise)
+        if len(z):
+            self.nav.set_measurements(z)
+            self.nav.step_async(u)
+        self.nav.append_map_history(time)
+
+    def finish_posted(self, waypoints):
+        """per frame (best pose | the best particle's path as of the frame's Update, as step_waypoints copies it), best map"""
+        self.nav.sync()   # (raises what a dropped step left)
+        out, best = [], 0   # BestParticle = 0 after reset (PHDNavigator.cs:265)
+        for k, (t, b, pose, model) in enumerate(self.nav.WayMaps()):
+            if waypoints:
+                times, poses, _ = self.nav.WayPointsAt(k + 1, [best])   # (entry 0 is start_waypoints')
+                out.append(((times, poses[0]), model))
+            else:
+                out.append((pose, model))
+            best = b
+        return out
+
+
+def replay(rec, particles, seed, solver_cls, estimate="poses", posted=False):
     if estimate not in ("poses", "waypoints"):
         raise ValueError("estimate is 'poses' or 'waypoints'")
     frames = frames_of(rec)
@@ -82,6 +112,8 @@ def replay(rec, particles, seed, solver_cls, estimate="poses"):
     solver = solver_cls(p, pose, particles)
     if estimate == "waypoints":
         solver.start_waypoints(len(frames) + 1)
+    if posted:
+        solver.start_posted(len(frames), len(frames) * p.max_components)
     rng = np.random.default_rng(seed)
     cfg = config_of(rec)
     chol = np.linalg.cholesky(cfg["MotionCovarianceMultiplier"] * np.array(cfg["MotionCovariance"], float))   # PHDNavigator.cs:257-259
@@ -92,14 +124,25 @@ def replay(rec, particles, seed, solver_cls, estimate="poses"):
         tprev = t
         noise = dt * (rng.normal(size=(particles, 6)) @ chol.T)     # Util.RandomGaussianVector, Util.cs:173-202
         u = float(rng.uniform(1e-6, 1.0))
-        if estimate == "waypoints":
+        if posted:
+            solver.post(t, reading, noise, z, u)
+        elif estimate == "waypoints":
             (wt, wp), bmap = solver.step_waypoints(t, reading, noise, z, u)
             history.append((t, [(float(a), np.array(b)) for a, b in zip(wt, wp)]))
         else:
             bpose, bmap = solver.step(reading, noise, z, u)
             trajectory.append((t, bpose))
             history.append((t, list(trajectory)))
-        maps.append((t, bmap))
+        if not posted:
+            maps.append((t, bmap))
+    if posted:
+        for (t, _, _), (est, bmap) in zip(frames, solver.finish_posted(estimate == "waypoints")):
+            if estimate == "waypoints":
+                history.append((t, [(float(a), np.array(b)) for a, b in zip(*est)]))
+            else:
+                trajectory.append((t, est))
+                history.append((t, list(trajectory)))
+            maps.append((t, bmap))
     return {"estimate.out": rio.serialize_trajectories(history), "maps.out": rio.serialize_maps(maps)}
 
 
@@ -147,13 +190,14 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out")
     ap.add_argument("--estimate", choices=("poses", "waypoints"), default="poses")
+    ap.add_argument("--posted", action="store_true", help="post the whole record without a host wait; the files are built from the device's logs")
     a = ap.parse_args()
     if a.make:
         print("wrote", make_synthetic_record(a.make, a.frames))
         if not a.record:
             return
     rec = rio.read_record(a.record)
-    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate)
+    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate, posted=a.posted)
     if a.out:
         rio.write_record(a.out, dict(rec, **out))
     maps = rio.map_history_from_descriptor(out["maps.out"])
