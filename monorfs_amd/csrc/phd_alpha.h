@@ -2039,7 +2039,8 @@ __global__ __launch_bounds__(256, 4) void k_quasi_setll(const DevParams prm, con
 #define PHD_DENS_WAVES 4
 #endif
 #ifndef PHD_DENS_PAIR
-#define PHD_DENS_PAIR 1   // two landmarks per lane for map estimates of at most DENS_JL landmarks (0: a landmark per lane, two components per trip)
+#define PHD_DENS_PAIR 2   // 2: two landmarks per lane for map estimates of at most DENS_JL landmarks, three for 80 < J <= 96;
+                          // 1: two everywhere up to DENS_JL; 0: a landmark per lane, two components per trip
 #endif
 #define DENS_LDS_DOUBLES (DENS_TILE * DENS_REC + 2 * (DENS_JL / 64) * 256 + EXPTAB_N + 2)
 // WeightAlpha's last line for a particle whose density sums and set log-likelihood come from two workgroups (k_particle_chain's helper
@@ -2086,8 +2087,10 @@ __device__ __forceinline__ double alpha_density_prestage(const StepBufs& a, doub
 
 // `meet` (the helper workgroup of k_particle_chain): the body ends with alpha_meet instead of WeightAlpha's last line; returns
 // whether this workgroup wrote the particle's alpha. `pre`: alpha_density_prestage has run on this pool (pre_pcount: what it returned).
-__device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const StepBufs& a, double* pool, int pin = -1, bool meet = false,
-                                                   bool pre = false, double pre_pcount = 0.0)
+// `triple`: the layout of 80 < J <= 96 (below) — a constant of the instance, alpha_density_body picks it.
+template <bool triple>
+__device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const StepBufs& a, double* pool, int pin, bool meet, bool pre,
+                                                     double pre_pcount)
 {
 	constexpr int JL = DENS_JL;
 	double* const tile = pool;                                        // [DENS_TILE][12]
@@ -2135,10 +2138,24 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 	// first exchanging the landmark slot they do not keep — lane l then holds slot l & (S - 1) of its wave's components, the
 	// layout the reduction below has always read. Which loop runs depends on J alone, so every workgroup that runs this body
 	// for a particle (k_alpha_density, the chain's main and helper workgroups) adds in the same order.
+	//
+	// 80 < J <= 96 — PHD_DENS_PAIR >= 2 —: the rule above gives a second block of S = 32 slots and every lane reads every record it is
+	// dealt twice, once per block. Here ONE block of 96 slots instead: lane jl = lane & 31 holds the landmarks jl, 32 + jl and 64 + jl,
+	// the two lane groups of a wave take different components (stride 8), a visit reads the record once for up to three evaluations.
+	// The six sums use the registers of the pair layout's eight. At the end of a sweep the two lane groups meet over 32 lanes and
+	// store the [JB][4][64] layout of the reduction below: block 0 as a pair block of 64 slots, block 1's sum whole on the lower lane
+	// group and 0.0 on the upper one, whose share the reduction adds. The second sweep's components — the corrected map's entries
+	// that are no misdetection copy — are first listed over the WHOLE map, in map order (16-bit indices in partcl, which the pair
+	// layouts do not touch before a sweep's end; the window counts in partpl, idle by then), and then staged in tiles of the list:
+	// a third of the corrected map is one tile where the windows of 256 map entries made three. A map of more entries than the list
+	// holds keeps the windows.
 	double plog_part = 0, clog_part = 0, pcount_part = pre ? pre_pcount : 0.0;
 	{
 		const int JB = (J + 63) >> 6;
 		const bool pair = PHD_DENS_PAIR && J > 0 && J <= JL;
+		constexpr int ULIST = (JL / 64) * 256 * 8 / 2;   // entries of the list of uncovered components: partcl's bytes / 2
+		unsigned short* const ulist = (unsigned short*) partcl;
+		int* const ucnt = (int*) partpl;                 // [window][wave] uncovered entries (ULIST / 256 windows at most)
 		// (the sum of the prior weights, sum w_pred: added up where the records are staged below — thread tid takes the
 		// components tid, tid + 256, ... there, in this order)
 		if (!pair) {
@@ -2150,7 +2167,8 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 		                                            // the block's landmarks: its first — a sum nobody reads)
 		bool ptwo[2] = {false, false};
 		double pacc[2][2] = {}, pcacc[2][2] = {};   // [block][landmark slot]: the sweep's sum; the corrected density's sum (both sweeps)
-		if (pair) {
+		                                            // (the triple layout: [0][0], [0][1], [1][0] for the landmarks jl, 32 + jl, 64 + jl)
+		if (pair && !triple) {
 #pragma unroll
 			for (int b = 0; b < 2; b++) {
 				const int rem = min(64, J - b * 64);
@@ -2204,8 +2222,73 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) visit(cc, false);
 			}
 		};
+		// the triple layout's share of a staged tile: every component of this lane's group at the lane's three landmarks (a slot
+		// beyond J: landmark 64 — a sum nobody reads)
+		auto triple_tile = [&](const bool first, const int cend) {
+			double xa[3], xb[3], xc[3];
+			const int jl = lane & 31;
+			unsigned int oa = 8u * jl, ob = 8u * (32 + jl), oc = 8u * ((64 + jl < J) ? 64 + jl : 64);
+			asm volatile("" : "+v"(oa), "+v"(ob), "+v"(oc));   // (as in pair_block: no addresses worked out ahead of the tile loop)
+#pragma unroll
+			for (int t = 0; t < 3; t++) {
+				const char* const row = (const char*) (lm + t * JS);
+				xa[t] = *(const double*) (row + oa);
+				xb[t] = *(const double*) (row + ob);
+				xc[t] = *(const double*) (row + oc);
+			}
+			for (int cc = wv * 2 + (lane >> 5); cc < cend; cc += 8) {
+				const double* tt = tile + cc * DENS_REC;
+				double g[DENS_REC - 1];   // the record, read once for the three landmarks (the weight ratio: first sweep only)
+#pragma unroll
+				for (int t = 0; t < DENS_REC - 1; t++) g[t] = (t < 10 || first) ? tt[t] : 0;
+				const double e1 = exp_pair(gauss_logw(g, xa[0] - g[0], xa[1] - g[1], xa[2] - g[2]), etab);
+				const double e2 = exp_pair(gauss_logw(g, xb[0] - g[0], xb[1] - g[1], xb[2] - g[2]), etab);
+				const double e3 = exp_pair(gauss_logw(g, xc[0] - g[0], xc[1] - g[1], xc[2] - g[2]), etab);
+				if (first) {
+					pacc[0][0] += e1;
+					pacc[0][1] += e2;
+					pacc[1][0] += e3;
+					pcacc[0][0] = fma(g[10], e1, pcacc[0][0]);
+					pcacc[0][1] = fma(g[10], e2, pcacc[0][1]);
+					pcacc[1][0] = fma(g[10], e3, pcacc[1][0]);
+				}
+				else {
+					pcacc[0][0] += e1;
+					pcacc[0][1] += e2;
+					pcacc[1][0] += e3;
+				}
+			}
+		};
 		for (int src = 0; src < 2; src++) {
-			const int total = (src == 0) ? np : no;
+			int total = (src == 0) ? np : no;
+			const bool listed = src == 1 && triple && no <= ULIST;
+			if (listed) {
+				// the corrected components not accounted for by the first sweep, over the whole map, in map order
+				const int nwin = (no + 255) >> 8;
+				unsigned int mine = 0;   // bit i: entry i * 256 + tid is one
+				unsigned int co = 4u * (unsigned int) tid;
+				asm volatile("" : "+v"(co));   // (a uniform base and a 32-bit offset, formed here: the thread's address in `cover`,
+				                               // worked out ahead of both sweeps, was spilled)
+				for (int i = 0; i < nwin; i++) {
+					const int c = i * 256 + tid;
+					const bool other = c < no && !*(const int*) ((const char*) cover + co + 1024u * i);
+					const unsigned long long bal = ballot64(other);
+					if (lane == 0) ucnt[i * 4 + wv] = __popcll(bal);
+					mine |= (other ? 1u : 0u) << i;
+				}
+				__syncthreads();
+				int base = 0;
+				for (int i = 0; i < nwin; i++) {
+					const bool other = (mine >> i) & 1u;
+					const unsigned long long bal = ballot64(other);
+					int slot = base + __popcll(bal & lanemask_lt());
+					for (int q = 0; q < wv; q++) slot += ucnt[i * 4 + q];
+					if (other) ulist[slot] = (unsigned short) (i * 256 + tid);
+					base += ucnt[i * 4] + ucnt[i * 4 + 1] + ucnt[i * 4 + 2] + ucnt[i * 4 + 3];
+				}
+				total = base;
+				__syncthreads();
+			}
 			for (int c0 = 0; c0 < total; c0 += DENS_TILE) {
 				int c = (DENS_TILE < 256 && tid >= DENS_TILE) ? total : c0 + tid;
 				int cend;
@@ -2233,6 +2316,15 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 					}
 					cend = min(DENS_TILE, total - c0);
 				}
+				else if (listed) {   // (a tile of the list)
+					cend = min(DENS_TILE, total - c0);
+					if (tid < cend) {
+						double w, m[3], P[6], Pi[6], det;
+						load_comp(vout.rec + (sbo + ulist[c0 + tid]) * MIX_REC, w, m, P);
+						inv_sym3(P, Pi, det);
+						gauss_record(w, m, Pi, PHD_INV_2PI / sqrt(fabs(det)), tile + tid * DENS_REC);
+					}
+				}
 				else {
 					// the corrected components not accounted for by the first sweep, compacted in map order
 					const bool other = c < total && !cover[c];
@@ -2250,7 +2342,11 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 					}
 				}
 				__syncthreads();
-				if (pair) {
+				if constexpr (triple) {
+					if (src == 0) triple_tile(true, cend);
+					else          triple_tile(false, cend);
+				}
+				else if (pair) {
 					if (src == 0) {
 						pair_block(0, true, cend);
 						if (JB > 1) pair_block(1, true, cend);
@@ -2260,7 +2356,7 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 						if (JB > 1) pair_block(1, false, cend);
 					}
 				}
-				for (int jb = 0; jb < JB && cend > 0 && !pair; jb++) {
+				for (int jb = 0; jb < JB && cend > 0 && !pair && !triple; jb++) {
 					const int rem = min(64, J - jb * 64);
 					const int LJ  = (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1))));
 					const int G   = 64 / LJ, g = lane / LJ, jl = lane & (LJ - 1);
@@ -2302,7 +2398,20 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 				}
 				__syncthreads();
 			}
-			if (pair) {
+			if constexpr (triple) {
+				// the sweep's sums, once: block 0 as a pair block of 64 slots (the lower lane group keeps landmark jl, the upper one
+				// 32 + jl, own + the other's), block 1 whole on the lower lane group
+				double* const part = (src == 0) ? partp : partc;
+				const double v0 = (src == 0) ? pacc[0][0] : pcacc[0][0], v1 = (src == 0) ? pacc[0][1] : pcacc[0][1];
+				const double v2 = (src == 0) ? pacc[1][0] : pcacc[1][0];
+				const bool upper = (lane & 32) != 0;
+				double keep = upper ? v1 : v0;
+				keep += __shfl_xor(upper ? v0 : v1, 32, 64);
+				part[wv * 64 + lane] = keep;
+				const double both = v2 + __shfl_xor(v2, 32, 64);
+				part[(4 + wv) * 64 + lane] = upper ? 0.0 : both;
+			}
+			else if (pair) {
 				// the sweep's sums, once: neighbouring lane groups hold the same two landmarks for different components — the even
 				// group keeps slot 0 and takes the odd group's, the odd group keeps slot 1 (own + the neighbour's)
 				double* const part = (src == 0) ? partp : partc;
@@ -2368,6 +2477,18 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
 	if (!meet) return true;
 	__syncthreads();
 	return s_wc[0] != 0;
+}
+
+// The body is compiled twice, the layout a constant of each instance, so that neither side carries the other's registers (the pair
+// layout's addresses and strides, the triple layout's third landmark: as a run-time flag of one loop it cost 40 bytes of scratch).
+// The WHOLE body: with the two sweeps alone compiled twice inside one body the other layouts' loops came out scheduled differently
+// from what they were (config S 0.7 % slower); this way their instance is the code it was before the triple layout existed.
+__device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const StepBufs& a, double* pool, int pin = -1, bool meet = false,
+                                                   bool pre = false, double pre_pcount = 0.0)
+{
+	const int J = a.aJ[(pin >= 0) ? pin : a.p0 + blockIdx.x];
+	if (PHD_DENS_PAIR >= 2 && J > 80 && J <= 96) return alpha_density_body_t<true>(prm, a, pool, pin, meet, pre, pre_pcount);
+	return alpha_density_body_t<false>(prm, a, pool, pin, meet, pre, pre_pcount);
 }
 
 __global__ __launch_bounds__(256, PHD_DENS_WAVES) void k_alpha_density(const DevParams prm, const StepBufs a)
