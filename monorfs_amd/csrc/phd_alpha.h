@@ -769,6 +769,28 @@ __host__ __device__ inline size_t alpha_jscratch_doubles(int Jcap) { return (siz
 // which then run BESIDE the association below instead of behind it; *helper_go says whether it did.
 __device__ __forceinline__ unsigned int my_xcd() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u; }   // HW_REG_XCC_ID
 
+// Sum over the workgroup's 256 threads in the order of the eight-level tree over red[256] (level s: red[t] += red[t + s] for t < s,
+// s = 128, 64, ..., 1; the result is red[0]), on three barriers instead of ten: levels 128 and 64 add across waves, wave 0 reads them
+// from LDS as (r[l] + r[l + 128]) + (r[l + 64] + r[l + 192]); levels 32 ... 1 stay inside the wave, v += shfl_down(v, s), where lane
+// 0's chain adds the pairs the tree added, in its order; lane 0 publishes the sum in red[0], and the last barrier frees `red` for its
+// next user. (Every wave adding for itself spares the publishing barrier and cost k_quasi_setll_grad 96 bytes of scratch.)
+__device__ __forceinline__ double block_tree_sum(double* red, double v, int tid)
+{
+	const int lane = tid & 63;
+	red[tid] = v;
+	__syncthreads();
+	if (tid < 64) {
+		double x = (red[lane] + red[lane + 128]) + (red[lane + 64] + red[lane + 192]);
+#pragma unroll
+		for (int s = 32; s > 0; s >>= 1) x += __shfl_down(x, s, 64);
+		if (lane == 0) red[0] = x;
+	}
+	__syncthreads();
+	const double r = red[0];
+	__syncthreads();
+	return r;
+}
+
 // does landmark j hold a detection entry: adj[j][MW] has a bit for every measurement inside its gate
 template <int MW>
 __device__ __forceinline__ bool has_detection(const unsigned long long* adj, int j)
@@ -790,7 +812,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 	double* zs   = smem + lay.zs;          // [MP][3] measurements
 	double* red  = smem + lay.red;         // [256] reduction scratch
 	double* etab = red;                    // [256] exp table (filled before the cluster sums, once `red` is idle)
-	__shared__ int s_J, s_changed, s_nroots, s_big;
+	__shared__ int s_J, s_changed[2], s_nroots, s_big;
 	__shared__ double s_ccount, s_total;
 	__shared__ int s_ebump, s_g2lds;                                                    // gradient mode (see the first pass below)
 	__shared__ double s_g2[GRAD ? QGRAD_G2_CLUSTERS * QGRAD_HDR + QGRAD_G2_WEIGHTS : 2];
@@ -816,17 +838,7 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 	double* sortw   = smem + lay.p1_sortw;             // [ncap] weights, stable descending
 	int*    sortsrc = (int*) (smem + lay.p1_sortsrc);  // [ncap]
 	// block-wide sum in a fixed order (thread partials, then a tree)
-	auto block_sum = [&](double v) {
-		red[tid] = v;
-		__syncthreads();
-		for (int s = 128; s > 0; s >>= 1) {
-			if (tid < s) red[tid] += red[tid + s];
-			__syncthreads();
-		}
-		double r = red[0];
-		__syncthreads();
-		return r;
-	};
+	auto block_sum = [&](double v) { return block_tree_sum(red, v, tid); };
 	double wpart = 0;
 	for (int c = tid; c < no; c += 256) {
 		double wc = a.outw[sbo + c];   // (k_prune_merge's plane of the pruned weights: the records themselves are read for the picks only)
@@ -870,14 +882,17 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		// are taken whole, the entries of that bin are ranked among themselves by (weight, map index) and the first `need` of
 		// them taken. (Eight passes of an 8-bit radix select before: three barriers each, 22 k of this kernel's 74 k cycles on
 		// config B.)
+		// The same histogram orders them: an entry of a higher bin is heavier than every entry of a lower one, so an entry's place
+		// in the order is the number of entries in the bins above its own — the scan's running count, kept per bin — plus its rank
+		// by (weight, map index) among the entries of its own bin, which are few. (Every selected entry counted the entries before
+		// it among ALL J before: J * J comparisons, 12 k cycles of instruction issue on config B, not of waiting.)
 		constexpr int HB = 500;
 		int* const hist   = (int*) red;                                   // [HB + 4] (`red` is idle between the block sums above and the exp table below)
-		int* const selidx = (int*) (smem + lay.p1_selidx);                // [J] selected components, unordered
-		int* const tl     = sortsrc;                                      // the threshold bin's entries (sortsrc is written only by the ordering below)
+		int* const selidx = (int*) (smem + lay.p1_selidx);                // [ncand] the entries of the threshold bin and the bins above, grouped by bin
+		int* const pre    = (int*) (smem + lay.p1_dw);                    // [HB] entries in the bins above bin b (`dw` in LDS is written only by the merge below)
 		int& s_T = hist[HB];
 		int& s_above = hist[HB + 1];
 		int& s_nt = hist[HB + 2];
-		int& s_ntaken = hist[HB + 3];
 		const unsigned int hbase = (unsigned int) (((unsigned long long) __double_as_longlong(prm.minw) << 1) >> 49);
 		auto bin_of = [&](double w) {
 			const unsigned int k = (unsigned int) (((unsigned long long) __double_as_longlong(w) << 1) >> 49);
@@ -900,44 +915,34 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 			int run = incl - mine;
 #pragma unroll
 			for (int q = 0; q < 8; q++) {
-				if (run < J && J <= run + cq[q]) { s_T = 511 - (8 * lane + q); s_above = run; }
+				const int b = 511 - (8 * lane + q);
+				if (b < HB) pre[b] = run;
+				if (run < J && J <= run + cq[q]) { s_T = b; s_above = run; s_nt = cq[q]; }
 				run += cq[q];
 			}
 		}
 		__syncthreads();
-		const int T = s_T, above = s_above, need = J - above;   // `need` of the threshold bin's entries are taken (1 <= need <= its count)
+		const int T = s_T, above = s_above;   // the first J - above of the threshold bin's entries are taken (at least one)
+		const int ncand = above + s_nt;       // the entries of the bins above and of the threshold bin
+		// grouped by bin: bin b fills [pre[b], pre[b] + its count), from the top down (its count in `hist` is the cursor)
 		for (int c = tid; c < no; c += 256) {
 			const int b = bin_of(keyw[c]);
-			if (b > T) selidx[atomicAdd(&s_ntaken, 1)] = c;            // (the bins above: in any order)
-			else if (b == T) tl[atomicAdd(&s_nt, 1)] = c;
+			if (b >= T) selidx[pre[b] + atomicSub(&hist[b], 1) - 1] = c;
 		}
 		__syncthreads();
-		const int nt = s_nt;
-		for (int t = tid; t < nt; t += 256) {
-			const int ct = tl[t];
-			const double wt = keyw[ct];
-			int rank = 0;
-			for (int u = 0; u < nt; u++) {
-				const int cu = tl[u];
-				const double wu = keyw[cu];
-				rank += (wu > wt || (wu == wt && cu < ct)) ? 1 : 0;
-			}
-			if (rank < need) selidx[above + rank] = ct;   // (the bins above filled [0, above); ranks are distinct)
-		}
-		__syncthreads();
-		// order the J selected by (weight desc, map index asc): every entry counts the entries before it
-		for (int t = tid; t < J; t += 256) {
-			const int ct = selidx[t];
-			const double wt = keyw[ct];
-			int rank = 0;
+		for (int e = tid; e < ncand; e += 256) {
+			const int ce = selidx[e];
+			const double we = keyw[ce];
+			const int b = bin_of(we);
+			const int lo = pre[b], hi = (b == T) ? ncand : pre[b - 1];   // (bin b - 1 starts where bin b ends)
+			int rank = lo;
 #pragma unroll 4
-			for (int u = 0; u < J; u++) {
+			for (int u = lo; u < hi; u++) {
 				const int cu = selidx[u];
 				const double wu = keyw[cu];
-				rank += (wu > wt || (wu == wt && cu < ct)) ? 1 : 0;
+				rank += (wu > we || (wu == we && cu < ce)) ? 1 : 0;
 			}
-			sortw[rank]   = wt;
-			sortsrc[rank] = ct;
+			if (rank < J) { sortw[rank] = we; sortsrc[rank] = ce; }   // (of the threshold bin, the first J - above)
 		}
 		__syncthreads();
 	}
@@ -1027,14 +1032,31 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 	}
 	__threadfence_block();
 	__syncthreads();
+	// The means of the picked records come from HBM, at addresses that depend on `pick`. The set-up of phase 3 that does not need
+	// them is done here, around that trip, by threads that wait for it or for the barrier anyway (the arrays of phase 1 it
+	// overwrites are dead behind the barrier above), not in the loop below that every landmark's chain of h, PD and the logarithms
+	// runs through. (Holding a thread's first mean in registers across ALL of the set-up cost 16 bytes of scratch.)
+	constexpr int JW = JL / 64;                                   // words of a transposed adjacency row (LDS case)
+	unsigned long long* adjT = (unsigned long long*) (smem + lay.p3_adjT);   // [MP][JW] landmarks gated with measurement k
+	for (int k = tid; k < M; k += 256) labz[k] = J + k;
+	for (int t = tid; t < MP * JW; t += 256) adjT[t] = 0;
+	if (tid == 0) { s_nroots = 0; s_big = 0; s_changed[0] = 0; }
 	for (int j = tid; j < J; j += 256) {
+		double2 r0 = {0.0, 0.0}, r1 = {0.0, 0.0};
+		if (!QUASI) {
+			const double2* rc = (const double2*) (vout.rec + (sbo + pick[j]) * MIX_REC);   // its mean: the first 32 bytes of the record
+			r0 = rc[0]; r1 = rc[1];
+		}
+#pragma unroll
+		for (int b = 0; b < MW; b++) adj[(size_t) j * MW + b] = 0;
+		labl[j] = j;
+		cnt[j]  = 0;
+		memL[j] = 0;
+		memZ[j] = 0;
 		if (QUASI) {
 			lm[j] = a.qlm[j * 3]; lm[JS + j] = a.qlm[j * 3 + 1]; lm[2 * JS + j] = a.qlm[j * 3 + 2];
 		}
 		else {
-			int c = pick[j];
-			const double2* rc = (const double2*) (vout.rec + (sbo + c) * MIX_REC);   // its mean: the first 32 bytes of the record
-			const double2 r0 = rc[0], r1 = rc[1];
 			double l0 = r0.y, l1 = r1.x, l2 = r1.y;
 			lm[j] = l0; lm[JS + j] = l1; lm[2 * JS + j] = l2;
 			double* glm = a.alm + (size_t) p * 3 * a.Jcap;   // for k_alpha_density
@@ -1066,26 +1088,22 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 	{
 		double* mats = xreg;   // [25][4] one 5x5 matrix per cluster of a tiny map (dead before the Murty path reuses the region)
 
-		constexpr int JW = JL / 64;                                   // words of a transposed adjacency row (LDS case)
-		unsigned long long* adjT = (unsigned long long*) (smem + lay.p3_adjT);   // [MP][JW] landmarks gated with measurement k
-		for (int j = tid; j < J; j += 256) {
+		// h(m_j) and the two logarithms of the detection probability. Up to 128 landmarks, two threads share a landmark: both
+		// compute PD (the same instructions on the same inputs), thread j takes log PD and thread j + 128 log(1 - PD).
+		const bool pair = J <= 128;
+		for (int t = tid; t < (pair ? 256 : J); t += 256) {
+			const int j = pair ? (t & 127) : t;
+			if (j >= J) continue;
 			double m[3] = {lm[j], lm[JS + j], lm[2 * JS + j]}, z[3], l[3];
 			measure_perfect(prm, pose, m, z, l);
 			const float dz = (!QUASI && DEPTH) ? depth_at(prm, z) : 0.0f;   // (the quasi set log-likelihood keeps the constant PD, :574-575)
-			zh[j] = z[0]; zh[JS + j] = z[1]; zh[2 * JS + j] = z[2];
 			const double pdv = QUASI ? prm.pd : detection_probability_m<!QUASI && DEPTH>(prm, z, dz);
-			lpd[j] = log(pdv);
-			lmd[j] = log(1 - pdv);
-#pragma unroll
-			for (int b = 0; b < MW; b++) adj[(size_t) j * MW + b] = 0;
-			labl[j] = j;
-			cnt[j]  = 0;
-			memL[j] = 0;
-			memZ[j] = 0;
+			if (!pair || t < 128) {
+				zh[j] = z[0]; zh[JS + j] = z[1]; zh[2 * JS + j] = z[2];
+				lpd[j] = log(pdv);
+			}
+			if (!pair || t >= 128) lmd[j] = log(1 - pdv);
 		}
-		for (int k = tid; k < M; k += 256) labz[k] = J + k;
-		for (int t = tid; t < MP * JW; t += 256) adjT[t] = 0;
-		if (tid == 0) { s_nroots = 0; s_big = 0; }
 		__threadfence_block();
 		__syncthreads();
 		// detection block: defined iff Mahalanobis(z_k; h(m_j), R) < 5 (:433-442). Measurement per lane, wave w takes the
@@ -1117,10 +1135,11 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		PHD_STAMP(4);
 		// connected components of the bipartite (landmark, measurement) graph by min-label propagation;
 		// a cluster's label ends as its smallest landmark index, which is also its position in the
-		// reference's component list (rows with detection entries are inserted first, ascending).
+		// reference's component list (rows with detection entries are inserted first, ascending). Two barriers an iteration: the
+		// iterations raise two change flags in turn, and the one an iteration does not use is lowered for the next in its second
+		// half, when every thread has read it (behind the first barrier) and none raises it yet (before the second).
 		for (int it = 0; it < J + M + 1; it++) {
-			if (tid == 0) s_changed = 0;
-			__syncthreads();
+			int* const changed = &s_changed[it & 1];
 			for (int j = tid; j < J; j += 256) {
 				int l = labl[j];
 #pragma unroll
@@ -1132,10 +1151,11 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 						l = min(l, labz[k]);
 					}
 				}
-				if (l < labl[j]) { labl[j] = l; s_changed = 1; }
+				if (l < labl[j]) { labl[j] = l; *changed = 1; }
 			}
 			__threadfence_block();
 			__syncthreads();
+			if (tid == 0) s_changed[(it & 1) ^ 1] = 0;
 			for (int k = tid; k < M; k += 256) {
 				int l = labz[k];
 				if (inlds) {
@@ -1154,12 +1174,11 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 						if ((adj[(size_t) j * MW + (k >> 6)] >> (k & 63)) & 1ull) l = min(l, labl[j]);
 					}
 				}
-				if (l < labz[k]) { labz[k] = l; s_changed = 1; }
+				if (l < labz[k]) { labz[k] = l; *changed = 1; }
 			}
 			__threadfence_block();
 			__syncthreads();
-			if (!s_changed) break;
-			__syncthreads();
+			if (!*changed) break;
 		}
 		// members of every cluster, appended in arrival order (sorted by the reader)
 		for (int j = tid; j < J; j += 256) {
@@ -2447,17 +2466,7 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 		}
 	}
 	// block reductions (fixed order)
-	auto block_sum = [&](double v) {
-		red[tid] = v;
-		__syncthreads();
-		for (int s = 128; s > 0; s >>= 1) {
-			if (tid < s) red[tid] += red[tid + s];
-			__syncthreads();
-		}
-		double r = red[0];
-		__syncthreads();
-		return r;
-	};
+	auto block_sum = [&](double v) { return block_tree_sum(red, v, tid); };
 	const double plog = block_sum(plog_part);
 	const double clog = block_sum(clog_part);
 	const double pcount = block_sum(pcount_part) + nb * prm.birthw;
