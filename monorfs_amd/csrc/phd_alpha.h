@@ -740,9 +740,22 @@ __host__ __device__ inline AlphaLds alpha_lds(int MP, int ncap)
 #define QGRAD_G2_CLUSTERS 64                                  // headers / weights of the first pass kept in LDS for the ordered replay
 #define QGRAD_G2_WEIGHTS 384
 #define QGRAD_HDR 10                                         // doubles per cluster in the particle's scratch: pairings, G[6], list offset, finite
-#ifndef DENS_JL
-#define DENS_JL 128   // landmarks whose partial sums stay in LDS
-#endif
+// The density sums (alpha_density_body, below the association): which lanes hold which landmarks is a function of the map estimate's
+// size J alone, so every workgroup that runs them for a particle (k_alpha_density, the chain's main and helper workgroups) adds in
+// the same order.
+constexpr int DENS_JL = 128;   // landmarks whose partial sums stay in LDS: two blocks of 64 (larger values: no gain)
+enum class DensLayout {
+	slab,     // J = 0 or J > DENS_JL: a landmark per lane; the partial sums beyond DENS_JL landmarks go through the particle's HBM slab
+	pair,     // two landmarks per lane
+	triple    // 80 < J <= 96: three landmarks per lane, one block of 96 slots
+};
+__host__ __device__ constexpr DensLayout dens_layout(int J)
+{
+	return (J <= 0 || J > DENS_JL) ? DensLayout::slab : (J > 80 && J <= 96) ? DensLayout::triple : DensLayout::pair;
+}
+// slots of a block of `rem` (of at most 64) landmarks: 64, or the power of two a last block's remainder rounds up to. The pair
+// layout's lanes, the slab layout's lanes and the reduction over a block's lanes all follow from it.
+__device__ __forceinline__ int dens_block_slots(int rem) { return (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1)))); }
 // Per-particle HBM slab (a.jscratch; ints packed two per double). Three users, never live together:
 //   the association body when J > ALPHA_JL: lm 3J, dw J, zh 3J, lpd J, res J, adj 4J | pick, dsrc, labl, roots: 4J ints | lmd, memL, memZ J, cnt J ints
 //   the gradient first pass (J <= ALPHA_JL, the arrays above are in LDS then): cluster headers | jpall | elist
@@ -1067,15 +1080,15 @@ __device__ __forceinline__ void alpha_assoc_body(const DevParams& prm, const Ste
 		// Everything the density sums read is final now: the pruned map, the births, and — just above — the map estimate. The
 		// helper gets them through the L2 both workgroups sit behind (so only a helper on this XCD is taken: no write-back of the
 		// L2, which cost more than the helper gives): every wave's stores have left the CU (vmcnt) before the barrier below, then
-		// thread 0 leaves the word the helper waits for. A map estimate beyond the densities' LDS arrays stays here (its sums would
-		// go through the slab this body is still using).
+		// thread 0 leaves the word the helper waits for. A map estimate of the slab layout (dens_layout) stays here: beyond the
+		// densities' LDS arrays its sums would go through the slab this body is still using, and J = 0 has no sums.
 		if (tid == 0) { a.aJ[p] = J; a.account[p] = s_ccount; }
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	}
 	__threadfence_block();
 	__syncthreads();
 	if (!QUASI && helper_go && tid == 0) {
-		const int go = (J > 0 && J <= DENS_JL && helper_word == ((a.dstamp << 4) | my_xcd())) ? 1 : 0;
+		const int go = (dens_layout(J) != DensLayout::slab && helper_word == ((a.dstamp << 4) | my_xcd())) ? 1 : 0;
 		__hip_atomic_store(a.dsync + 3 * (size_t) p + 1, 2u * a.dstamp + (unsigned int) go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		*helper_go = go;
 #ifdef PHD_STAMPS   // (diagnostic build, PHD_STAMP_KERNEL=5: was the helper taken, and when — 100 MHz ticks; see k_particle_chain)
@@ -2047,21 +2060,50 @@ __global__ __launch_bounds__(256, 4) void k_quasi_setll(const DevParams prm, con
 // k_alpha_density — the two mixture-density sums of WeightAlpha (PHDNavigator.cs:381-384) and its last line:
 //   alpha = exp( L(Z | map estimate, pose) + [sum_j log v_pred(m_j) - sum w_pred] - [sum_j log v_corr(m_j) - sum w_corr] )
 // with v(.) the full, ungated mixture density (Map.Evaluate(point), Map.cs:192-202) and m_j the landmarks of
-// the map estimate left in HBM by k_alpha_assoc. Landmark per lane, component tiles broadcast from LDS.
+// the map estimate left in HBM by k_alpha_assoc. Component tiles are staged once and broadcast from LDS; which lanes hold which
+// landmarks is DensLayout's matter (dens_layout, next to DENS_JL above).
 // =================================================================================================
 #define DENS_REC 12   // gauss_record + the weight ratio of the component's surviving misdetection copy (+ 1: records stay 16-byte aligned)
-
-#ifndef DENS_TILE
-#define DENS_TILE TILE   // components staged per tile of THIS kernel (threads beyond it sit the staging out)
-#endif
+constexpr int DENS_TILE = TILE;   // components staged per tile of THIS kernel
+static_assert(DENS_TILE == 256, "the density sums stage one record per thread of the workgroup");
 #ifndef PHD_DENS_WAVES
 #define PHD_DENS_WAVES 4
 #endif
-#ifndef PHD_DENS_PAIR
-#define PHD_DENS_PAIR 2   // 2: two landmarks per lane for map estimates of at most DENS_JL landmarks, three for 80 < J <= 96;
-                          // 1: two everywhere up to DENS_JL; 0: a landmark per lane, two components per trip
-#endif
-#define DENS_LDS_DOUBLES (DENS_TILE * DENS_REC + 2 * (DENS_JL / 64) * 256 + EXPTAB_N + 2)
+
+// The kernel's LDS (the chain's pool while the body runs), and what reuses a part of it while that part is idle.
+struct DensLds {
+	double* tile;            // [DENS_TILE][DENS_REC] the staged records
+	double* partp;           // [DENS_JL / 64][4][64] partial densities of v_pred, [block][wave][lane] (the HBM slab takes over when J > DENS_JL)
+	double* partc;           // the same for v_corr
+	double* etab;            // [EXPTAB_N] exp_pair's table
+	int*    wc;              // [4] per wave: the uncovered entries of the window being compacted
+	double* red;             // over tile: block_tree_sum's scratch, free once both sweeps are over
+	unsigned short* ulist;   // over partc: the list of uncovered entries, free until the second sweep publishes (the pair and triple layouts write partc only then)
+	int*    ucnt;            // over partp: [window][wave] the list's counts, free once the first sweep's logarithms are taken
+	int*    met;             // over wc[0]: alpha_meet's answer for the workgroup, free once the last window is compacted
+	static constexpr int part = (DENS_JL / 64) * 256;
+	static constexpr int ULIST = part * 8 / 2;   // entries of the list: partc's bytes / 2
+	static constexpr int o_partp = DENS_TILE * DENS_REC, o_partc = o_partp + part, o_etab = o_partc + part, o_wc = o_etab + EXPTAB_N;
+	static constexpr int doubles = o_wc + 2;
+};
+constexpr int DENS_LDS_DOUBLES = DensLds::doubles;
+static_assert(DENS_LDS_DOUBLES * 8 == 34832, "the density sums' LDS: four workgroups per CU, and chain_lds_bytes counts on it");
+static_assert(DensLds::ULIST / 256 * 4 * 4 <= DensLds::part * 8 && 256 <= DensLds::o_partp, "DensLds: an alias passes the array under it");
+
+__device__ __forceinline__ DensLds dens_lds(double* pool)
+{
+	DensLds l;
+	l.tile  = pool;
+	l.partp = pool + DensLds::o_partp;
+	l.partc = pool + DensLds::o_partc;
+	l.etab  = pool + DensLds::o_etab;
+	l.wc    = (int*) (pool + DensLds::o_wc);
+	l.red   = l.tile;
+	l.ulist = (unsigned short*) l.partc;
+	l.ucnt  = (int*) l.partp;
+	l.met   = l.wc;
+	return l;
+}
 // WeightAlpha's last line for a particle whose density sums and set log-likelihood come from two workgroups (k_particle_chain's helper
 // and main): each leaves its number (a.ratio / a.setll), waits until that store is in the L2 both sit behind and swaps the launch's
 // number into the particle's ticket word; the one that finds it there already is second, reads the other's number and writes alpha
@@ -2079,45 +2121,128 @@ __device__ __forceinline__ bool alpha_meet(const StepBufs& a, int p, bool have_r
 	return true;
 }
 
+// A component (w, m, P) as the DENS_REC record the sweeps read: slots 0 - 9, gauss_record's. Slot 10, the weight ratio of the
+// component's misdetection copy, and the spare slot 11 are the caller's.
+__device__ __forceinline__ void dens_stage(double w, const double m[3], const double P[6], double* rec)
+{
+	double Pi[6], det;
+	inv_sym3(P, Pi, det);
+	gauss_record(w, m, Pi, PHD_INV_2PI / sqrt(fabs(det)), rec);
+}
+// The same from a mixture's record; returns the component's weight.
+__device__ __forceinline__ double dens_stage(const double* comp, double* rec)
+{
+	double w, m[3], P[6];
+	load_comp(comp, w, m, P);
+	dens_stage(w, m, P, rec);
+	return w;
+}
+
 // What alpha_density_body can do before the step has produced anything (the helper workgroup of k_particle_chain, while it waits):
 // the exponent table and the records of the PRIOR components of its first tile — they only need the prior mixture —, the
 // component's weight kept in the record's spare slot. Returns the thread's share of sum w_pred so far; the body is then called
 // with `pre` = true and that number and leaves those records as they are (the same arithmetic, done earlier).
 __device__ __forceinline__ double alpha_density_prestage(const StepBufs& a, double* pool, int p)
 {
-	double* const tile = pool;
-	double* const etab = tile + DENS_TILE * DENS_REC + 2 * (DENS_JL / 64) * 256;
+	const DensLds L = dens_lds(pool);
 	const int tid = threadIdx.x;
 	const MixView vin = bank_view(a, SEL_IN);
 	const int n = vin.count[p];
 	const size_t sbi = in_base(a, p);
-	exp_tab_init(etab, tid);
+	exp_tab_init(L.etab, tid);
 	double pc = 0;
-	if (tid < DENS_TILE && tid < n) {
-		double w, m[3], P[6], Pi[6], det;
-		load_comp(vin.rec + (sbi + tid) * MIX_REC, w, m, P);
-		pc = w;
-		inv_sym3(P, Pi, det);
-		gauss_record(w, m, Pi, PHD_INV_2PI / sqrt(fabs(det)), tile + tid * DENS_REC);
-		tile[tid * DENS_REC + 11] = w;
+	if (tid < n) {
+		pc = dens_stage(vin.rec + (sbi + tid) * MIX_REC, L.tile + tid * DENS_REC);
+		L.tile[tid * DENS_REC + 11] = pc;
 	}
 	return pc;
 }
 
+// One staged record at the K landmarks x[0 .. K) of a lane (K = 1, 2, 3): the record is read once for all of them, its weight
+// ratio in the first sweep only. acc: the sweep's sums; cacc: the corrected density's sums. Most components of the corrected map are
+// the misdetection copies of predicted components that came through PruneModel alone: the same Gaussian with the weight (1 - PD) w.
+// Their densities are not evaluated again: the first sweep, over the predicted mixture, adds ratio_c * (w_c N_c(m_j)) to the corrected
+// sum as well, ratio_c = wcopy[c] / w_c (k_prune_merge, which also checks that the copy's moments are the component's up to Merge's
+// rounding). The second sweep takes only the other corrected components (updated by a measurement, merged).
+template <int K>
+__device__ __forceinline__ void dens_visit(const double* rec, const double* etab, const double (*x)[3], const bool first, double* acc,
+                                           double* cacc)
+{
+	double g[DENS_REC - 1], e[K];
+#pragma unroll
+	for (int t = 0; t < DENS_REC - 1; t++) g[t] = (t < 10 || first) ? rec[t] : 0;
+#pragma unroll
+	for (int k = 0; k < K; k++) e[k] = exp_pair(gauss_logw(g, x[k][0] - g[0], x[k][1] - g[1], x[k][2] - g[2]), etab);
+#pragma unroll
+	for (int k = 0; k < K; k++) {
+		if (first) {
+			acc[k] += e[k];
+			cacc[k] = fma(g[10], e[k], cacc[k]);
+		}
+		else cacc[k] += e[k];
+	}
+}
+
+// The second sweep's components are the corrected map's entries that are no misdetection copy of a predicted component
+// ("uncovered", !cover[c]), compacted in map order in windows of 256 entries, an entry per thread: dens_window_count leaves the
+// window's count per wave in cnt[4]; behind a barrier, dens_window_slot gives the thread's entry its place among the window's
+// uncovered ones, and their number.
+__device__ __forceinline__ unsigned long long dens_window_count(bool other, int* cnt)
+{
+	const unsigned long long bal = ballot64(other);
+	if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = __popcll(bal);
+	return bal;
+}
+__device__ __forceinline__ int dens_window_slot(unsigned long long bal, const int* cnt, int& count)
+{
+	const int wv = threadIdx.x >> 6;
+	int slot = __popcll(bal & lanemask_lt());
+	for (int q = 0; q < wv; q++) slot += cnt[q];
+	count = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+	return slot;
+}
+
+// The triple layout compacts the WHOLE map first, into a list of 16-bit indices (in partc, which the pair and triple layouts do not
+// touch before a sweep's end; the window counts in partp, idle by then), and then stages tiles of the list: a third of the
+// corrected map is one tile where the windows of 256 map entries made three. Returns the list's length. (A map of more than
+// DensLds::ULIST entries keeps the windows.)
+__device__ __forceinline__ int dens_list_uncovered(const DensLds& L, const int* cover, int no)
+{
+	const int tid = threadIdx.x;
+	const int nwin = (no + 255) >> 8;
+	unsigned int mine = 0;   // bit i: entry i * 256 + tid is one
+	unsigned int co = 4u * (unsigned int) tid;
+	asm volatile("" : "+v"(co));   // (a uniform base and a 32-bit offset, formed here: the thread's address in `cover`,
+	                               // worked out ahead of both sweeps, was spilled)
+	for (int i = 0; i < nwin; i++) {
+		const int c = i * 256 + tid;
+		const bool other = c < no && !*(const int*) ((const char*) cover + co + 1024u * i);
+		dens_window_count(other, L.ucnt + i * 4);
+		mine |= (other ? 1u : 0u) << i;
+	}
+	__syncthreads();
+	int base = 0;
+	for (int i = 0; i < nwin; i++) {
+		const bool other = (mine >> i) & 1u;
+		int count;
+		const int slot = base + dens_window_slot(ballot64(other), L.ucnt + i * 4, count);
+		if (other) L.ulist[slot] = (unsigned short) (i * 256 + tid);
+		base += count;
+	}
+	__syncthreads();
+	return base;
+}
+
 // `meet` (the helper workgroup of k_particle_chain): the body ends with alpha_meet instead of WeightAlpha's last line; returns
 // whether this workgroup wrote the particle's alpha. `pre`: alpha_density_prestage has run on this pool (pre_pcount: what it returned).
-// `triple`: the layout of 80 < J <= 96 (below) — a constant of the instance, alpha_density_body picks it.
+// `triple`: dens_layout(J) is DensLayout::triple — a constant of the instance, alpha_density_body picks it.
 template <bool triple>
 __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const StepBufs& a, double* pool, int pin, bool meet, bool pre,
                                                      double pre_pcount)
 {
-	constexpr int JL = DENS_JL;
-	double* const tile = pool;                                        // [DENS_TILE][12]
-	double* const partpl = tile + DENS_TILE * DENS_REC;                    // [JB][4][64] partial densities of v_pred (HBM slab when J > JL)
-	double* const partcl = partpl + (JL / 64) * 256;                  // the same for v_corr
-	double* const etab = partcl + (JL / 64) * 256;
-	int* const s_wc = (int*) (etab + EXPTAB_N);                       // [4]
-	double* red = tile;                          // reduction scratch once the sweeps are over
+	const DensLds L = dens_lds(pool);
+	double* const tile = L.tile;
+	const double* const etab = L.etab;
 
 	const int p = (pin >= 0) ? pin : a.p0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const int cap = a.cap;
@@ -2131,68 +2256,47 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 	const int JS = a.Jcap;
 	const double* lm = a.alm + (size_t) p * 3 * JS;   // [3][Jcap]
 	double* gj = a.jscratch + (size_t) p * alpha_jscratch_doubles(a.Jcap);
-	double* partp = (J <= JL) ? partpl : gj + AlphaSlab::partp * (size_t) JS;   // (the association kernel's arrays in the slab are dead by now)
-	double* partc = (J <= JL) ? partcl : gj + AlphaSlab::partc * (size_t) JS;
+	double* partp = (J <= DENS_JL) ? L.partp : gj + AlphaSlab::partp * (size_t) JS;   // (the association kernel's arrays in the slab are dead by now)
+	double* partc = (J <= DENS_JL) ? L.partc : gj + AlphaSlab::partc * (size_t) JS;
 	const double* wcopy = a.wcopy + (size_t) p * (cap + a.Mcap);
 	const int* cover = a.cover + sbo;
-	if (!pre) exp_tab_init(etab, tid);
+	if (!pre) exp_tab_init(L.etab, tid);
 	__syncthreads();
 
-	// ---- phase 2: sum_j log v_pred(m_j), sum_j log v_corr(m_j) with v = full ungated mixture density (Map.cs:192-202)
-	// Component tiles are staged once and swept for every block of 64 landmarks (landmark per lane, the
-	// component broadcast from LDS). A last block with few landmarks is packed: LJ = 2^k lanes carry the
-	// landmarks and the 64 / LJ lane groups take different components, then the groups are summed.
-	//
-	// Most components of the corrected map are the misdetection copies of predicted components that came through
-	// PruneModel alone: the same Gaussian with the weight (1 - PD) w. Their densities are not evaluated again: the sweep
-	// over the predicted mixture adds ratio_c * (w_c N_c(m_j)) to the corrected sum as well, ratio_c = wcopy[c] / w_c
-	// (k_prune_merge, which also checks that the copy's moments are the component's up to Merge's rounding). The second
-	// sweep takes only the other corrected components (updated by a measurement, merged).
-	//
-	// Map estimates of at most JL landmarks (two blocks) — PHD_DENS_PAIR —: a lane holds TWO landmarks of a block. A block of S
-	// slots (64, or the power of two the remainder rounds up to) is LJ = S / 2 lanes with the landmarks jl and LJ + jl on lane jl,
-	// and the 64 / LJ lane groups of a wave take different components: the same (component, landmark) evaluations per trip as two
-	// components for one landmark each, for ONE record read per lane. The sums of both blocks stay in registers over a whole
-	// sweep (the tile loop outermost: records are staged once) and go to partp / partc once per sweep, neighbouring lane groups
-	// first exchanging the landmark slot they do not keep — lane l then holds slot l & (S - 1) of its wave's components, the
-	// layout the reduction below has always read. Which loop runs depends on J alone, so every workgroup that runs this body
-	// for a particle (k_alpha_density, the chain's main and helper workgroups) adds in the same order.
-	//
-	// 80 < J <= 96 — PHD_DENS_PAIR >= 2 —: the rule above gives a second block of S = 32 slots and every lane reads every record it is
-	// dealt twice, once per block. Here ONE block of 96 slots instead: lane jl = lane & 31 holds the landmarks jl, 32 + jl and 64 + jl,
-	// the two lane groups of a wave take different components (stride 8), a visit reads the record once for up to three evaluations.
-	// The six sums use the registers of the pair layout's eight. At the end of a sweep the two lane groups meet over 32 lanes and
-	// store the [JB][4][64] layout of the reduction below: block 0 as a pair block of 64 slots, block 1's sum whole on the lower lane
-	// group and 0.0 on the upper one, whose share the reduction adds. The second sweep's components — the corrected map's entries
-	// that are no misdetection copy — are first listed over the WHOLE map, in map order (16-bit indices in partcl, which the pair
-	// layouts do not touch before a sweep's end; the window counts in partpl, idle by then), and then staged in tiles of the list:
-	// a third of the corrected map is one tile where the windows of 256 map entries made three. A map of more entries than the list
-	// holds keeps the windows.
+	// ---- phase 2: sum_j log v_pred(m_j), sum_j log v_corr(m_j) with v = full ungated mixture density (Map.cs:192-202). Two sweeps:
+	// over the predicted mixture — which also accounts for its components' misdetection copies in the corrected map, dens_visit —
+	// and over the corrected map's other entries. The tile loop is outermost: component tiles are staged once and swept for every
+	// landmark, by the layout dens_layout(J) names.
 	double plog_part = 0, clog_part = 0, pcount_part = pre ? pre_pcount : 0.0;
 	{
 		const int JB = (J + 63) >> 6;
-		const bool pair = PHD_DENS_PAIR && J > 0 && J <= JL;
-		constexpr int ULIST = (JL / 64) * 256 * 8 / 2;   // entries of the list of uncovered components: partcl's bytes / 2
-		unsigned short* const ulist = (unsigned short*) partcl;
-		int* const ucnt = (int*) partpl;                 // [window][wave] uncovered entries (ULIST / 256 windows at most)
+		const bool pair = dens_layout(J) != DensLayout::slab;   // (the triple layout's instance: always)
 		// (the sum of the prior weights, sum w_pred: added up where the records are staged below — thread tid takes the
 		// components tid, tid + 256, ... there, in this order)
+		// The slab layout (the loop over jb in the tile loop below): a landmark per lane, every block of 64 landmarks sweeps the tile,
+		// two independent components per trip. A last block with few landmarks is packed: LJ = dens_block_slots lanes carry the
+		// landmarks and the 64 / LJ lane groups take different components. The tile's sums are added to the lane's own slot of
+		// partp / partc, zeroed here.
 		if (!pair) {
 			for (int i = tid; i < JB * 256; i += 256) { partp[i] = 0; partc[i] = 0; }
 		}
-		// the pair layout of block b: lane group width, first component and stride of this lane, its two landmarks
+		// The pair layout: a lane holds TWO landmarks of a block. A block of S slots (dens_block_slots) is LJ = S / 2 lanes with the
+		// landmarks jl and LJ + jl on lane jl, and the 64 / LJ lane groups of a wave take different components: the same (component,
+		// landmark) evaluations per trip as two components for one landmark each, for ONE record read per lane. The sums of both
+		// blocks stay in registers over a whole sweep. Of block b: lane group width, first component and stride of this lane, its
+		// two landmarks
 		int  plj[2] = {1, 1}, pcc[2] = {0, 0}, pstep[2] = {256, 256};
 		unsigned int pj[2][2] = {};                 // [block][landmark slot]: the landmark's byte offset in a row of lm (a slot beyond
 		                                            // the block's landmarks: its first — a sum nobody reads)
 		bool ptwo[2] = {false, false};
 		double pacc[2][2] = {}, pcacc[2][2] = {};   // [block][landmark slot]: the sweep's sum; the corrected density's sum (both sweeps)
-		                                            // (the triple layout: [0][0], [0][1], [1][0] for the landmarks jl, 32 + jl, 64 + jl)
+		double tacc[3] = {}, tcacc[3] = {};         // the triple layout's, [landmark slot]: the landmarks jl, 32 + jl, 64 + jl
 		if (pair && !triple) {
 #pragma unroll
 			for (int b = 0; b < 2; b++) {
 				const int rem = min(64, J - b * 64);
 				if (rem <= 0) continue;
-				const int S = (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1))));
+				const int S = dens_block_slots(rem);
 				ptwo[b] = S > 1;
 				const int lj = ptwo[b] ? (S >> 1) : 1, G = 64 / lj, jl = lane & (lj - 1);
 				plj[b] = lj;
@@ -2205,111 +2309,46 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 		// one block's share of a staged tile: every component of this lane's group at the lane's landmarks (their coordinates
 		// are read here, per tile, so that they do not live through the staging: twelve doubles from the cache)
 		auto pair_block = [&](const int b, const bool first, const int cend) {
-			double xa[3], xb[3];
+			double x[2][3];
 			unsigned int oa = pj[b][0], ob = pj[b][1];
 			asm volatile("" : "+v"(oa), "+v"(ob));   // (or six addresses per block are worked out ahead of the tile loop and spilled)
 #pragma unroll
 			for (int t = 0; t < 3; t++) {
 				const char* const row = (const char*) (lm + t * JS);   // (a uniform base and a 32-bit byte offset per lane)
-				xa[t] = *(const double*) (row + oa);
-				xb[t] = *(const double*) (row + ob);
+				x[0][t] = *(const double*) (row + oa);
+				x[1][t] = *(const double*) (row + ob);
 			}
-			auto visit = [&](const int cc, const bool two) {
-				const double* tt = tile + cc * DENS_REC;
-				double g[DENS_REC - 1];   // the record, read once for both landmarks (the weight ratio: first sweep only)
-#pragma unroll
-				for (int t = 0; t < DENS_REC - 1; t++) g[t] = (t < 10 || first) ? tt[t] : 0;
-				const double e1 = exp_pair(gauss_logw(g, xa[0] - g[0], xa[1] - g[1], xa[2] - g[2]), etab);
-				const double e2 = two ? exp_pair(gauss_logw(g, xb[0] - g[0], xb[1] - g[1], xb[2] - g[2]), etab) : 0.0;
-				if (first) {
-					pacc[b][0] += e1;
-					pcacc[b][0] = fma(g[10], e1, pcacc[b][0]);
-					if (two) {
-						pacc[b][1] += e2;
-						pcacc[b][1] = fma(g[10], e2, pcacc[b][1]);
-					}
-				}
-				else {
-					pcacc[b][0] += e1;
-					if (two) pcacc[b][1] += e2;
-				}
-			};
 			if (ptwo[b]) {
-				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) visit(cc, true);
+				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) dens_visit<2>(tile + cc * DENS_REC, etab, x, first, pacc[b], pcacc[b]);
 			}
 			else {   // (a block of one landmark: one per lane, 64 lane groups)
-				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) visit(cc, false);
+				for (int cc = pcc[b]; cc < cend; cc += pstep[b]) dens_visit<1>(tile + cc * DENS_REC, etab, x, first, pacc[b], pcacc[b]);
 			}
 		};
-		// the triple layout's share of a staged tile: every component of this lane's group at the lane's three landmarks (a slot
-		// beyond J: landmark 64 — a sum nobody reads)
+		// The triple layout, 80 < J <= 96, where the pair layout has a second block of S = 32 slots and every lane reads every record
+		// it is dealt twice, once per block. ONE block of 96 slots instead: lane jl = lane & 31 holds the landmarks jl, 32 + jl and
+		// 64 + jl, the two lane groups of a wave take different components (stride 8), a visit reads the record once for up to three
+		// evaluations. Its share of a staged tile (a slot beyond J: landmark 64 — a sum nobody reads):
 		auto triple_tile = [&](const bool first, const int cend) {
-			double xa[3], xb[3], xc[3];
+			double x[3][3];
 			const int jl = lane & 31;
 			unsigned int oa = 8u * jl, ob = 8u * (32 + jl), oc = 8u * ((64 + jl < J) ? 64 + jl : 64);
 			asm volatile("" : "+v"(oa), "+v"(ob), "+v"(oc));   // (as in pair_block: no addresses worked out ahead of the tile loop)
 #pragma unroll
 			for (int t = 0; t < 3; t++) {
 				const char* const row = (const char*) (lm + t * JS);
-				xa[t] = *(const double*) (row + oa);
-				xb[t] = *(const double*) (row + ob);
-				xc[t] = *(const double*) (row + oc);
+				x[0][t] = *(const double*) (row + oa);
+				x[1][t] = *(const double*) (row + ob);
+				x[2][t] = *(const double*) (row + oc);
 			}
-			for (int cc = wv * 2 + (lane >> 5); cc < cend; cc += 8) {
-				const double* tt = tile + cc * DENS_REC;
-				double g[DENS_REC - 1];   // the record, read once for the three landmarks (the weight ratio: first sweep only)
-#pragma unroll
-				for (int t = 0; t < DENS_REC - 1; t++) g[t] = (t < 10 || first) ? tt[t] : 0;
-				const double e1 = exp_pair(gauss_logw(g, xa[0] - g[0], xa[1] - g[1], xa[2] - g[2]), etab);
-				const double e2 = exp_pair(gauss_logw(g, xb[0] - g[0], xb[1] - g[1], xb[2] - g[2]), etab);
-				const double e3 = exp_pair(gauss_logw(g, xc[0] - g[0], xc[1] - g[1], xc[2] - g[2]), etab);
-				if (first) {
-					pacc[0][0] += e1;
-					pacc[0][1] += e2;
-					pacc[1][0] += e3;
-					pcacc[0][0] = fma(g[10], e1, pcacc[0][0]);
-					pcacc[0][1] = fma(g[10], e2, pcacc[0][1]);
-					pcacc[1][0] = fma(g[10], e3, pcacc[1][0]);
-				}
-				else {
-					pcacc[0][0] += e1;
-					pcacc[0][1] += e2;
-					pcacc[1][0] += e3;
-				}
-			}
+			for (int cc = wv * 2 + (lane >> 5); cc < cend; cc += 8) dens_visit<3>(tile + cc * DENS_REC, etab, x, first, tacc, tcacc);
 		};
 		for (int src = 0; src < 2; src++) {
 			int total = (src == 0) ? np : no;
-			const bool listed = src == 1 && triple && no <= ULIST;
-			if (listed) {
-				// the corrected components not accounted for by the first sweep, over the whole map, in map order
-				const int nwin = (no + 255) >> 8;
-				unsigned int mine = 0;   // bit i: entry i * 256 + tid is one
-				unsigned int co = 4u * (unsigned int) tid;
-				asm volatile("" : "+v"(co));   // (a uniform base and a 32-bit offset, formed here: the thread's address in `cover`,
-				                               // worked out ahead of both sweeps, was spilled)
-				for (int i = 0; i < nwin; i++) {
-					const int c = i * 256 + tid;
-					const bool other = c < no && !*(const int*) ((const char*) cover + co + 1024u * i);
-					const unsigned long long bal = ballot64(other);
-					if (lane == 0) ucnt[i * 4 + wv] = __popcll(bal);
-					mine |= (other ? 1u : 0u) << i;
-				}
-				__syncthreads();
-				int base = 0;
-				for (int i = 0; i < nwin; i++) {
-					const bool other = (mine >> i) & 1u;
-					const unsigned long long bal = ballot64(other);
-					int slot = base + __popcll(bal & lanemask_lt());
-					for (int q = 0; q < wv; q++) slot += ucnt[i * 4 + q];
-					if (other) ulist[slot] = (unsigned short) (i * 256 + tid);
-					base += ucnt[i * 4] + ucnt[i * 4 + 1] + ucnt[i * 4 + 2] + ucnt[i * 4 + 3];
-				}
-				total = base;
-				__syncthreads();
-			}
+			const bool listed = src == 1 && triple && no <= DensLds::ULIST;
+			if (listed) total = dens_list_uncovered(L, cover, no);
 			for (int c0 = 0; c0 < total; c0 += DENS_TILE) {
-				int c = (DENS_TILE < 256 && tid >= DENS_TILE) ? total : c0 + tid;
+				const int c = c0 + tid;
 				int cend;
 				if (src == 0) {
 					if (pre && c0 == 0 && c < n) {   // (staged ahead: only the copy's weight ratio is new)
@@ -2317,7 +2356,7 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 						tile[tid * DENS_REC + 10] = (w > 0) ? wcopy[c] / w : 0.0;
 					}
 					else if (c < total) {
-						double w, m[3], P[6], Pi[6], det;
+						double w, m[3], P[6];
 						if (c < n) {
 							load_comp(vin.rec + (sbi + c) * MIX_REC, w, m, P);
 							pcount_part += w;
@@ -2329,36 +2368,21 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 #pragma unroll
 							for (int t = 0; t < 6; t++) P[t] = prm.birthP[t];
 						}
-						inv_sym3(P, Pi, det);
-						gauss_record(w, m, Pi, PHD_INV_2PI / sqrt(fabs(det)), tile + tid * DENS_REC);
+						dens_stage(w, m, P, tile + tid * DENS_REC);
 						tile[tid * DENS_REC + 10] = (w > 0) ? wcopy[c] / w : 0.0;
 					}
 					cend = min(DENS_TILE, total - c0);
 				}
 				else if (listed) {   // (a tile of the list)
 					cend = min(DENS_TILE, total - c0);
-					if (tid < cend) {
-						double w, m[3], P[6], Pi[6], det;
-						load_comp(vout.rec + (sbo + ulist[c0 + tid]) * MIX_REC, w, m, P);
-						inv_sym3(P, Pi, det);
-						gauss_record(w, m, Pi, PHD_INV_2PI / sqrt(fabs(det)), tile + tid * DENS_REC);
-					}
+					if (tid < cend) dens_stage(vout.rec + (sbo + L.ulist[c0 + tid]) * MIX_REC, tile + tid * DENS_REC);
 				}
-				else {
-					// the corrected components not accounted for by the first sweep, compacted in map order
+				else {               // (a window of the map, compacted here)
 					const bool other = c < total && !cover[c];
-					const unsigned long long bal = ballot64(other);
-					if (lane == 0) s_wc[wv] = __popcll(bal);
+					const unsigned long long bal = dens_window_count(other, L.wc);
 					__syncthreads();
-					int slot = __popcll(bal & lanemask_lt());
-					for (int q = 0; q < wv; q++) slot += s_wc[q];
-					cend = s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
-					if (other) {
-						double w, m[3], P[6], Pi[6], det;
-						load_comp(vout.rec + (sbo + c) * MIX_REC, w, m, P);
-						inv_sym3(P, Pi, det);
-						gauss_record(w, m, Pi, PHD_INV_2PI / sqrt(fabs(det)), tile + slot * DENS_REC);
-					}
+					const int slot = dens_window_slot(bal, L.wc, cend);
+					if (other) dens_stage(vout.rec + (sbo + c) * MIX_REC, tile + slot * DENS_REC);
 				}
 				__syncthreads();
 				if constexpr (triple) {
@@ -2377,7 +2401,7 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 				}
 				for (int jb = 0; jb < JB && cend > 0 && !pair && !triple; jb++) {
 					const int rem = min(64, J - jb * 64);
-					const int LJ  = (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1))));
+					const int LJ  = dens_block_slots(rem);
 					const int G   = 64 / LJ, g = lane / LJ, jl = lane & (LJ - 1);
 					const bool jv = jl < rem;
 					const int  j  = jb * 64 + jl;
@@ -2418,11 +2442,11 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 				__syncthreads();
 			}
 			if constexpr (triple) {
-				// the sweep's sums, once: block 0 as a pair block of 64 slots (the lower lane group keeps landmark jl, the upper one
-				// 32 + jl, own + the other's), block 1 whole on the lower lane group
+				// the sweep's sums into the [JB][4][64] layout the reduction below reads, once: the two lane groups meet over 32 lanes —
+				// block 0 as a pair block of 64 slots (the lower lane group keeps landmark jl, the upper one 32 + jl, own + the
+				// other's), block 1's sum whole on the lower lane group and 0.0 on the upper one, whose share the reduction adds
 				double* const part = (src == 0) ? partp : partc;
-				const double v0 = (src == 0) ? pacc[0][0] : pcacc[0][0], v1 = (src == 0) ? pacc[0][1] : pcacc[0][1];
-				const double v2 = (src == 0) ? pacc[1][0] : pcacc[1][0];
+				const double v0 = (src == 0) ? tacc[0] : tcacc[0], v1 = (src == 0) ? tacc[1] : tcacc[1], v2 = (src == 0) ? tacc[2] : tcacc[2];
 				const bool upper = (lane & 32) != 0;
 				double keep = upper ? v1 : v0;
 				keep += __shfl_xor(upper ? v0 : v1, 32, 64);
@@ -2432,7 +2456,8 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 			}
 			else if (pair) {
 				// the sweep's sums, once: neighbouring lane groups hold the same two landmarks for different components — the even
-				// group keeps slot 0 and takes the odd group's, the odd group keeps slot 1 (own + the neighbour's)
+				// group keeps slot 0 and takes the odd group's, the odd group keeps slot 1 (own + the neighbour's); lane l then holds
+				// slot l & (S - 1) of its wave's components, the layout the reduction below reads
 				double* const part = (src == 0) ? partp : partc;
 #pragma unroll
 				for (int b = 0; b < 2; b++) {
@@ -2449,10 +2474,12 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 			}
 			__threadfence_block();
 			__syncthreads();
+			// sum_j log v(m_j): wave w takes the blocks w, w + 4, ... — the four waves' sums, then the lane groups' by shuffles, then the
+			// logarithm on the lanes that carry a landmark
 			const double* part = (src == 0) ? partp : partc;
 			for (int jb = wv; jb < JB; jb += 4) {
 				const int rem = min(64, J - jb * 64);
-				const int LJ  = (rem > 32) ? 64 : ((rem <= 1) ? 1 : (1 << (32 - __clz(rem - 1))));
+				const int LJ  = dens_block_slots(rem);
 				const int jl = lane & (LJ - 1);
 				double v = part[(jb * 4 + 0) * 64 + lane] + part[(jb * 4 + 1) * 64 + lane] + part[(jb * 4 + 2) * 64 + lane] +
 				           part[(jb * 4 + 3) * 64 + lane];
@@ -2466,7 +2493,7 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 		}
 	}
 	// block reductions (fixed order)
-	auto block_sum = [&](double v) { return block_tree_sum(red, v, tid); };
+	auto block_sum = [&](double v) { return block_tree_sum(L.red, v, tid); };
 	const double plog = block_sum(plog_part);
 	const double clog = block_sum(clog_part);
 	const double pcount = block_sum(pcount_part) + nb * prm.birthw;
@@ -2475,7 +2502,7 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 		double ratio = (plog - pcount) - (clog - ccount);   // :390
 		if (meet) {
 			__hip_atomic_store(a.ratio + p, ratio, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			s_wc[0] = alpha_meet(a, p, true, ratio) ? 1 : 0;
+			L.met[0] = alpha_meet(a, p, true, ratio) ? 1 : 0;
 		}
 		else {
 			double alpha = exp(a.setll[p] + ratio);         // :392
@@ -2485,7 +2512,7 @@ __device__ __forceinline__ bool alpha_density_body_t(const DevParams& prm, const
 	}
 	if (!meet) return true;
 	__syncthreads();
-	return s_wc[0] != 0;
+	return L.met[0] != 0;
 }
 
 // The body is compiled twice, the layout a constant of each instance, so that neither side carries the other's registers (the pair
@@ -2496,7 +2523,7 @@ __device__ __forceinline__ bool alpha_density_body(const DevParams& prm, const S
                                                    bool pre = false, double pre_pcount = 0.0)
 {
 	const int J = a.aJ[(pin >= 0) ? pin : a.p0 + blockIdx.x];
-	if (PHD_DENS_PAIR >= 2 && J > 80 && J <= 96) return alpha_density_body_t<true>(prm, a, pool, pin, meet, pre, pre_pcount);
+	if (dens_layout(J) == DensLayout::triple) return alpha_density_body_t<true>(prm, a, pool, pin, meet, pre, pre_pcount);
 	return alpha_density_body_t<false>(prm, a, pool, pin, meet, pre, pre_pcount);
 }
 

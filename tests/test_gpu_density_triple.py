@@ -14,12 +14,15 @@ import functools
 import numpy as np
 import pytest
 
+import orc
+
 pytestmark = pytest.mark.gpu
 
 from monorfs_amd.synth import Frame
 from test_gpu_density_layout import _check, _oracle, _params, _reference, _sized_case, nav_mod  # noqa: F401  (nav_mod: the fixture)
 
 LO, HI = 80, 96   # the triple layout: LO < J <= HI
+FAR_COV_LONG, NLIGHT_LONG = 4.0, 1950
 
 
 def _uncovered(pred, pruned):
@@ -141,6 +144,90 @@ def test_births_are_the_last_short_tile(nav_mod, monkeypatch):
     npred, _, unc = _counts(mixes)
     assert f.C == 256 and 256 < min(npred) and max(npred) < 512, npred
     assert min(unc) > 0, unc
+    _check(nav_mod, monkeypatch, f, p, alpha, setll)
+
+
+ULIST = 2048   # entries the list of uncovered components holds (DensLds::ULIST); a longer corrected map keeps the windows of 256
+
+
+@functools.lru_cache(maxsize=None)
+def _long_map_case(J, nvis, M, vis_cov, far_cov, nlight, clutter, seed):
+    """_built_case's frame for two particles with `nlight` more components beyond the range clip: light (2 to 2.4 MinWeight, all
+    distinct: the prune keeps them, the map estimate does not take them), narrow and spread over 4 - 40 m (none close enough to
+    another to be merged). They lengthen the pruned corrected map and nothing else. MaxQuantity and the component capacity are
+    raised to `cap`, the next multiple of 64 above the predicted mixture. Returns the corrected mixtures as well."""
+    nfar = max(2, int(np.ceil(J / 0.9)))
+    C = nvis + nfar + nlight
+    f = Frame(2, C, M, seed, weight_profile="steady")
+    rng = np.random.default_rng(seed + 1)
+    idx = np.arange(C)
+    far, light = idx >= nvis, idx >= nvis + nfar
+    heavy = far & ~light
+    rngs = np.linalg.norm(f.mean, axis=2, keepdims=True)
+    f.mean[:, heavy] *= rng.uniform(2.5, 3.5, (1, int(heavy.sum()), 1)) / rngs[:, heavy]     # range clip: 2 m
+    f.mean[:, light] *= rng.uniform(4.0, 40.0, (1, nlight, 1)) / rngs[:, light]
+    f.cov = np.array(f.cov)
+    f.cov[:, heavy] *= far_cov
+    f.cov[:, light] *= 0.01
+    f.cov[:, ~far] *= vis_cov
+    u = rng.uniform(0.85, 1.0, C)
+    cap = (C + M + 63) // 64 * 64
+    p = _params(f, clutter_density=clutter, max_components=cap, max_quantity=cap)
+    wl = 2.0 * p.min_weight * u / 0.85
+    s = (J + 0.5 - wl[light].sum()) / u[heavy].sum()
+    for _ in range(12):
+        f.w = np.broadcast_to(np.where(light, wl, np.where(far, u * s, 0.05 * u)), (2, C)).copy()
+        mixes, corrected = [], []
+        for i in range(f.P):
+            pred = orc.predict(p, f.poses[i], f.z, f.map(i))
+            corrected.append(orc.correct(p, f.poses[i], f.z, pred))
+            mixes.append((pred, orc.prune(p, corrected[-1])))
+        tot = np.array([pr[0].sum() for _, pr in mixes])
+        if tot.min() > J + 0.15 and tot.max() < J + 0.85:
+            break
+        s += (J + 0.5 - tot.mean()) / u[heavy].sum()
+    return f, p, mixes, corrected
+
+
+def _absorbed_rows(p, corrected, pruned):
+    """the rows of the prune's cut (the corrected entries of at least MinWeight, heaviest first) that another row absorbed: the
+    rows whose mean is no entry's of the pruned map; and the number of rows"""
+    w, m = corrected[0], corrected[1]
+    keep = w >= p.min_weight
+    m = m[keep][np.argsort(-w[keep], kind="stable")][:p.max_quantity]
+    gone = [k for k, x in enumerate(m) if np.abs(pruned[1] - x).max(axis=1).min() > 1e-9 * max(1.0, np.abs(x).max())]
+    return gone, len(m)
+
+
+def test_corrected_map_longer_than_the_list(nav_mod, monkeypatch):
+    """A pruned corrected map of slightly more than ULIST entries (2 particles, J = 88, some 1950 light components beyond the range
+    clip): the list cannot hold their indices, and the triple layout's second sweep falls back to one compaction per window of 256
+    map entries. 32 wide visible components under 24 measurements, as in test_uncovered_entries_span_two_tiles: hundreds of
+    detection updates that weigh in the corrected density at the landmarks — without the uncovered entries behind the first
+    window the oracle's alpha moves by more than a thousand times the tolerance, which is asserted.
+
+    What the case stays clear of: a cut of more than 2048 rows in k_prune_merge loses row k + 2048 with every absorbed row k (its
+    absorbed flags are one 32-bit word per lane; to be fixed on its own). No row below (rows - 2048) is absorbed here, asserted
+    from the oracle's corrected and pruned maps, so the pruned map is the oracle's and the density sums are what is tested."""
+    f, p, mixes, corrected = _long_map_case(88, 32, 24, 100.0, FAR_COV_LONG, NLIGHT_LONG, 3e-7, 7600)
+    alpha, setll, Js = _reference(p, f, mixes)
+    assert Js == [88] * f.P, Js
+    _, no, unc = _counts(mixes)
+    assert min(no) > ULIST and max(no) <= p.max_quantity, no
+    for i, (pred, pr) in enumerate(mixes):
+        gone, rows = _absorbed_rows(p, corrected[i], pr)
+        assert rows > ULIST and all(k >= rows - 2048 for k in gone), (rows, gone[:8])
+        # the second sweep matters beyond its first window: alpha without the uncovered entries from map position 256 on
+        pm, pc = pred[1], pred[2].reshape(len(pred[1]), -1)
+        covered = np.array([bool((np.all(np.abs(pm - m) <= 1e-9 * np.abs(m), axis=1) &
+                                  np.all(np.abs(pc - c.reshape(-1)) <= 1e-9 * max(abs(c[0, 0]), abs(c[1, 1]), abs(c[2, 2])), axis=1)).any())
+                            for m, c in zip(pr[1], pr[2])])
+        sel = covered | (np.arange(len(covered)) < 256)
+        assert (~sel).sum() > 0
+        a_cut, _ = orc.weight_alpha(p, f.poses[i], f.z, pred, (pr[0][sel], pr[1][sel], pr[2][sel]))
+        assert abs(a_cut - alpha[i]) > 1e-3 * alpha[i], (a_cut, alpha[i])
+    state = orc.State
+    monkeypatch.setattr(orc, "State", lambda P, cap: state(P, max(cap, p.max_components)))   # (_check's oracle state: room for this map)
     _check(nav_mod, monkeypatch, f, p, alpha, setll)
 
 
