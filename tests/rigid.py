@@ -19,7 +19,7 @@ import orc
 from monorfs_amd.abi import prm3d_defaults
 from monorfs_amd.synth import measure_to_map_identity
 from test_gpu_shape_edges import frame, klass, path_of, perturbed
-from test_oracle_crosscheck import multiplier
+from test_oracle_crosscheck import gate2, multiplier
 
 S = np.sqrt(0.5)
 POSES = {   # unit quaternions (w, x, y, z), but for the last
@@ -154,7 +154,7 @@ def correct_sources(p, pose, z, pred):
     src, det = list(range(n)), [False] * n
     for zk in z:
         x = orc.measure_to_map(p, pose, zk)
-        near = np.nonzero(np.sum((pred[1] - x) ** 2, axis=1) <= p.density_distance_threshold)[0]
+        near = np.nonzero(np.sum((pred[1] - x) ** 2, axis=1) <= gate2(p))[0]
         src += list(near)
         det += [True] * len(near)
     return np.array(src), np.array(det)
@@ -184,7 +184,7 @@ def assert_bites(p, f, i, nramp=FULL_RAMP):
         "%d components at PD 0, %d of them behind the camera" % (np.count_nonzero(zero), np.count_nonzero(zero & (zh[:, 2] < 0)))
     both = 0
     for zk in f.z:
-        near = np.sum((m - orc.measure_to_map(p, pose, zk)) ** 2, axis=1) <= p.density_distance_threshold
+        near = np.sum((m - orc.measure_to_map(p, pose, zk)) ** 2, axis=1) <= gate2(p)
         both += bool(np.any(near & zero) and np.any(near & ramp))
     assert both >= 1, "no measurement gates a PD 0 component together with a ramp component"
     pred = orc.predict(p, pose, f.z, (w, m, c))
@@ -196,7 +196,7 @@ def assert_bites(p, f, i, nramp=FULL_RAMP):
 
 def explored_density(p, pose, z, mix):
     """Map.Evaluate(x, 3 DensityDistanceThreshold) at the map point of every measurement (PHDNavigator.cs:956-959, the
-    squared-Euclidean gate of Map.Near)"""
+    gate of Map.Near in p's metric: test_oracle_crosscheck.gate2)"""
     w, m, c = mix
     out = np.zeros(len(z))
     if len(w) == 0:
@@ -205,7 +205,7 @@ def explored_density(p, pose, z, mix):
     inv = np.linalg.inv(c)
     for k, zk in enumerate(z):
         d = orc.measure_to_map(p, pose, zk) - m
-        near = np.sum(d * d, axis=1) <= 3 * p.density_distance_threshold
+        near = np.sum(d * d, axis=1) <= gate2(p, 3)
         out[k] = np.sum((w * mult * np.exp(-0.5 * np.einsum("na,nab,nb->n", d, inv, d)))[near])
     return out
 
@@ -215,15 +215,30 @@ def off(x, edge, rel):
     return bool(np.all(np.abs(np.asarray(x, float) - edge) > rel * edge))
 
 
-def assert_margins(p, pose, z, mix, what="", scale=1.0):
+def assert_gate_margins(p, pose, z, mix, pred, what="", scale=1.0):
+    """no squared distance between a measurement's map point and a component on the gate of the correction (the predicted
+    components) or of the explored density (the prior ones, three radii), 1e-9 relative: test_oracle_crosscheck.gate2"""
+    for means, factor, name in ((pred[1], 1, "correction"), (mix[1], 3, "exploration")):
+        g = gate2(p, factor)
+        if len(means) == 0 or not np.isfinite(g):
+            continue
+        for zk in z:
+            d2 = np.sum((means - orc.measure_to_map(p, pose, zk)) ** 2, axis=1)
+            assert off(d2, g, 1e-9 * scale), "%s: a distance on the %s gate" % (what, name)
+
+
+def assert_margins(p, pose, z, mix, what="", scale=1.0, exempt=()):
     """no input of one particle's stages on a discrete edge, on the oracle's numbers: corrected weights against MinWeight,
     the explored density against ExplorationThreshold, the Mahalanobis distances of the set log-likelihood against its
-    gate of 5 (all 1e-6; 1e-6 relative for the first two; times `scale`). Returns the oracle's (predicted, corrected, pruned, alpha,
-    set log-likelihood)."""
+    gate of 5 (all 1e-6; 1e-6 relative for the first two; times `scale`), the gated distances against the gate of p's
+    metric (assert_gate_margins). exempt: indices into the corrected mixture that the MinWeight margin leaves out (entries
+    a frame plants ON MinWeight). Returns the oracle's (predicted, corrected, pruned, alpha, set log-likelihood)."""
     assert off(explored_density(p, pose, z, mix), p.exploration_threshold, 1e-6 * scale), what + ": an explored density on ExplorationThreshold"
     pred = orc.predict(p, pose, z, mix)
+    assert_gate_margins(p, pose, z, mix, pred, what, scale)
     cor = orc.correct(p, pose, z, pred)
-    assert off(cor[0], p.min_weight, 1e-6 * scale), what + ": a corrected weight on MinWeight"
+    checked = np.delete(cor[0], np.asarray(exempt, int)) if len(exempt) else cor[0]
+    assert off(checked, p.min_weight, 1e-6 * scale), what + ": a corrected weight on MinWeight"
     pr = orc.prune(p, cor)
     lm, _ = orc.best_map_estimate(pr)
     if len(lm) and len(z):

@@ -168,46 +168,61 @@ def random_case(rng, p, J, M, pose=None):
     return pose, lm, np.array(z)
 
 
-@pytest.mark.parametrize("seed", range(12))
-def test_set_log_likelihood_against_all_permutations(seed):
+# The bodies of the tests below take the parameter block (and the case generator): tests/test_oracle_param_space.py runs
+# them away from the defaults.
+def check_set_log_likelihood(p, seed, case=None):
     rng = np.random.default_rng(100 + seed)
-    p = prm3d_defaults(4, 600, 8)
     J = int(rng.integers(1, 4))
     M = int(rng.integers(1, 6 - J))          # J + M <= 5: 120 permutations at most
-    pose, lm, z = random_case(rng, p, J, M)
+    pose, lm, z = (case or random_case)(rng, p, J, M)
     if seed % 3 == 0 and J >= 2:            # two landmarks sharing a measurement: a cluster with 3 rows
         lm[1] = lm[0] + rng.normal(0, 1e-3, 3)
     want = set_log_likelihood_bruteforce(p, pose, lm, z)
     got = orc.set_log_likelihood(p, pose, lm, z)[0]
     assert np.isclose(got, want, rtol=1e-10, atol=1e-10), (got, want)
+    return got
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_set_log_likelihood_against_all_permutations(seed):
+    check_set_log_likelihood(prm3d_defaults(4, 600, 8), seed)
+
+
+def check_quasi_set_log_likelihood(p, seed, case=None):
+    rng = np.random.default_rng(500 + seed)
+    J = int(rng.integers(1, 4))
+    M = int(rng.integers(1, 6 - J))
+    pose, lm, z = (case or random_case)(rng, p, J, M)
+    if seed % 2:                               # a measurement 8 sigma off: inside the gate of 12, outside the gate of 5
+        # (through a Cholesky factor of R: a Mahalanobis distance of 8 whatever R's correlations; a diagonal R gives
+        # 8 sqrt(R_xx) along x as before)
+        z[0] = measure_perfect(p, pose, lm[0]) + np.linalg.cholesky(np.array(p.R).reshape(3, 3)) @ [8.0, 0.0, 0.0]
+    want = set_log_likelihood_bruteforce(p, pose, lm, z, quasi=True)
+    got = orc.quasi_set_log_likelihood(p, pose, lm, z)
+    assert np.isclose(got, want, rtol=1e-10, atol=1e-10), (got, want)
+    return got
 
 
 @pytest.mark.parametrize("seed", range(8))
 def test_quasi_set_log_likelihood_against_all_permutations(seed):
     """QuasiSetLogLikelihood (PHDNavigator.cs:526-713, value): constant PD, gate 12; landmarks near the border of the
     field of view, where the plain set log-likelihood would fade them out, count fully"""
-    rng = np.random.default_rng(500 + seed)
-    p = prm3d_defaults(4, 600, 8)
-    J = int(rng.integers(1, 4))
-    M = int(rng.integers(1, 6 - J))
-    pose, lm, z = random_case(rng, p, J, M)
-    if seed % 2:                               # a measurement 8 sigma off: inside the gate of 12, outside the gate of 5
-        z[0] = measure_perfect(p, pose, lm[0]) + 8 * np.sqrt(np.diag(np.array(p.R).reshape(3, 3))) * [1, 0, 0]
-    want = set_log_likelihood_bruteforce(p, pose, lm, z, quasi=True)
-    got = orc.quasi_set_log_likelihood(p, pose, lm, z)
-    assert np.isclose(got, want, rtol=1e-10, atol=1e-10), (got, want)
+    check_quasi_set_log_likelihood(prm3d_defaults(4, 600, 8), seed)
 
 
-def test_measurement_model_against_second_reading():
+def check_measurement_model(p, case=None):
     rng = np.random.default_rng(5)
-    p = prm3d_defaults(4, 600, 8)
     for _ in range(20):
-        pose, lm, _ = random_case(rng, p, 3, 1)
+        pose, lm, _ = (case or random_case)(rng, p, 3, 1)
         for x in lm:
             assert np.allclose(orc.measure_perfect(p, pose, x), measure_perfect(p, pose, x), rtol=1e-12, atol=1e-12)
             assert np.allclose(orc.jacobian_l(p, pose, x).reshape(3, 3), jacobian_l(p, pose, x), rtol=1e-11, atol=1e-11)
             assert np.isclose(orc.detection_probability(p, pose, x), detection_probability_m(p, measure_perfect(p, pose, x)),
                               rtol=1e-12, atol=1e-15)
+
+
+def test_measurement_model_against_second_reading():
+    check_measurement_model(prm3d_defaults(4, 600, 8))
 
 
 def random_mixture(rng, means, wlo, whi):
@@ -229,15 +244,12 @@ def test_best_map_estimate_literal_list(seed):
     assert list(gsrc) == wsrc and np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_weight_alpha_against_second_reading(seed):
-    """alpha = exp( L(Z | J, x) + [sum_j log v_pred(m_j) - sum w_pred] - [sum_j log v_corr(m_j) - sum w_corr] )
-    (PHDNavigator.cs:373-393) with the full, ungated mixture densities (Map.cs:192-202)."""
+def check_weight_alpha(p, seed, case=None):
+    """False: the case is outside the exact-enumeration regime and nothing was compared"""
     rng = np.random.default_rng(300 + seed)
-    p = prm3d_defaults(4, 600, 8)
     J = int(rng.integers(1, 4))
     M = int(rng.integers(1, 6 - J))
-    pose, lm, z = random_case(rng, p, J, M)
+    pose, lm, z = (case or random_case)(rng, p, J, M)
     nextra = int(rng.integers(0, 3))
     pred = random_mixture(rng, np.vstack([lm, lm[:nextra] + 0.3]), 0.3, 0.9)
     corr = random_mixture(rng, np.vstack([lm, lm[:nextra] + 0.3]), 0.02, 0.2)
@@ -245,13 +257,33 @@ def test_weight_alpha_against_second_reading(seed):
     jm, _ = best_map_estimate(corr)
     sll = set_log_likelihood_bruteforce(p, pose, jm, z) if len(jm) + M <= 5 else None
     if sll is None:
-        pytest.skip("case outside the exact-enumeration regime")
+        return False
     plog = sum(np.log(mixture(x, pred)) for x in jm)
     clog = sum(np.log(mixture(x, corr)) for x in jm)
     want = np.exp(sll + (plog - np.sum(pred[0])) - (clog - np.sum(corr[0])))
     got, gsll = orc.weight_alpha(p, pose, z, pred, corr)
     assert np.isclose(gsll, sll, rtol=1e-10, atol=1e-10)
     assert np.isclose(got, want, rtol=1e-9, atol=0), (got, want)
+    return True
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_weight_alpha_against_second_reading(seed):
+    """alpha = exp( L(Z | J, x) + [sum_j log v_pred(m_j) - sum w_pred] - [sum_j log v_corr(m_j) - sum w_corr] )
+    (PHDNavigator.cs:373-393) with the full, ungated mixture densities (Map.cs:192-202)."""
+    if not check_weight_alpha(prm3d_defaults(4, 600, 8), seed):
+        pytest.skip("case outside the exact-enumeration regime")
+
+
+def gate2(p, factor=1.0):
+    """the bound on |x - m|^2 of Map.Near / Map.Evaluate(x, radius) at radius = factor * DensityDistanceThreshold: Accord's
+    KDTree compares ITS distance with the radius — the squared one under the squared-Euclidean metric (the default), the
+    plain one under the Euclidean metric; no gate: infinity"""
+    from monorfs_amd.abi import PHD_GATE_DISABLED, PHD_GATE_SQUARED_EUCLIDEAN
+    r = factor * p.density_distance_threshold
+    if p.gate_metric == PHD_GATE_DISABLED:
+        return np.inf
+    return r if p.gate_metric == PHD_GATE_SQUARED_EUCLIDEAN else r * r
 
 
 def numpy_correct(p, pose, z, pred, by_value):
@@ -260,7 +292,7 @@ def numpy_correct(p, pose, z, pred, by_value):
     `qindex` (a Dictionary<Gaussian, int>, :854, :868, with Gaussian.Equals / GetHashCode comparing weight, mean and
     covariance exactly, Gaussian.cs:436-489) does: bit-identical components then share the index of the last of them."""
     R = np.array(p.R).reshape(3, 3)
-    gate = p.density_distance_threshold               # squared-Euclidean metric by default (Map.Near, :882)
+    gate = gate2(p)                                   # squared-Euclidean metric by default (Map.Near, :882)
     comps = []
     zh, H, S, PD = [], [], [], []
     qindex = {}
@@ -285,11 +317,9 @@ def numpy_correct(p, pose, z, pred, by_value):
     return comps
 
 
-@pytest.mark.parametrize("seed", range(4))
-def test_prm3d_correct_against_second_reading(seed):
+def check_prm3d_correct(p, seed, case=None):
     rng = np.random.default_rng(400 + seed)
-    p = prm3d_defaults(4, 600, 8)
-    pose, lm, z = random_case(rng, p, 3, 3)
+    pose, lm, z = (case or random_case)(rng, p, 3, 3)
     pred = random_mixture(rng, lm, 0.3, 1.1)
     comps = numpy_correct(p, pose, z, pred, by_value=False)
     ow, om, oc = orc.correct(p, pose, z, pred)
@@ -298,6 +328,12 @@ def test_prm3d_correct_against_second_reading(seed):
         assert np.isclose(ow[i], w, rtol=1e-9, atol=1e-300), (i, ow[i], w)
         assert np.allclose(om[i], m, rtol=1e-9, atol=1e-12)
         assert np.allclose(oc[i], P, rtol=1e-8, atol=1e-14)
+    return ow, len(pred[0])
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_prm3d_correct_against_second_reading(seed):
+    check_prm3d_correct(prm3d_defaults(4, 600, 8), seed)
 
 
 @pytest.mark.parametrize("seed", range(3))
@@ -331,18 +367,16 @@ def _qexp(w):
     return np.array([1.0, 0, 0, 0]) if a == 0 else np.concatenate([[np.cos(a)], np.sin(a) * w / a])
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_quasi_gradient_is_the_derivative_the_jacobian_describes(seed):
+def check_quasi_gradient(p, seed, case=None):
     """QuasiSetLogLikelihood(..., out gradient) (PHDNavigator.cs:543-713) with MeasurementJacobianP
     (PRM3DMeasurer.cs:185-211): [-R(q*) | -R(q*) [l - t]x] is the derivative of the local landmark coordinates wrt. a
     GLOBAL translation and wrt. a global-frame rotation applied as q' = exp(-w/2) q (not the convention of Pose3D.Add,
     which the restatement does not repair). With weights that sum to one (average_mode 1) the gradient of a case whose
     components are all enumerated must therefore equal central differences of the value along exactly those paths."""
     rng = np.random.default_rng(900 + seed)
-    p = prm3d_defaults(4, 600, 8)
     J = int(rng.integers(1, 4))
     M = int(rng.integers(1, 6 - J))
-    pose, lm, z = random_case(rng, p, J, M)
+    pose, lm, z = (case or random_case)(rng, p, J, M)
     pose[3:] /= np.linalg.norm(pose[3:])
     if seed % 2 and J >= 2:
         lm[1] = lm[0] + rng.normal(0, 1e-3, 3)         # a shared measurement: several pairings carry weight
@@ -359,6 +393,12 @@ def test_quasi_gradient_is_the_derivative_the_jacobian_describes(seed):
             l.append(set_log_likelihood_bruteforce(p, np.concatenate([pose[:3] + d[:3], q]), lm, z, quasi=True))
         num[i] = (l[0] - l[1]) / (2 * eps)
     assert np.allclose(grad, num, rtol=2e-5, atol=2e-4), (grad, num)
+    return grad
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_quasi_gradient_is_the_derivative_the_jacobian_describes(seed):
+    check_quasi_gradient(prm3d_defaults(4, 600, 8), seed)
 
 
 def test_tempered_average_as_written():
