@@ -63,6 +63,8 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_map_history_append(HandleRef nav, double time);
 	[DllImport(Lib)] public extern static int    phd_map_history(HandleRef nav, out int length, out IntPtr times, out IntPtr best, out IntPtr bestpose7, out IntPtr counts, out IntPtr offsets,
 	                                                              out IntPtr w, out IntPtr mean3, out IntPtr cov9);
+	[DllImport(Lib)] public extern static int    phd_map_error(HandleRef nav, IntPtr truth3, int ntruth, double cutoff, double order, IntPtr alignpose7, IntPtr hasreference,
+	                                                            out int length, out IntPtr times, out IntPtr ospa, out IntPtr cardinality, out IntPtr spatial, out IntPtr estimatesize);
 }
 
 /// <summary>
@@ -285,6 +287,26 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 			maps.Add(Tuple.Create(t[k], b[k], state, map));
 		}
 		return maps;
+	}
+
+	/// <summary>≙ Plot.MapError (postanalysis/Plot.cs:478-529) over the map log, on the device (phd_map_error; waits for it): per
+	/// entry (time, OSPA, cardinality part, spatial part, size of Map.BestMapEstimate) against `truth`, the visited map, with
+	/// cut-off c and order p. align: null, or per entry the estimated and the true pose at the reference time (14 doubles);
+	/// hasreference: null (every entry is aligned) or one byte per entry.</summary>
+	public List<Tuple<double, double, double, double, int>> MapError(List<double[]> truth, double c, double p, double[] align, byte[] hasreference)
+	{
+		double[] t3 = new double[3 * truth.Count];
+		for (int i = 0; i < truth.Count; i++) { truth[i].CopyTo(t3, 3 * i); }
+		int length; IntPtr times, ospa, card, spatial, sizes;
+		fixed (double* pt = t3) fixed (double* pa = align) fixed (byte* ph = hasreference) {
+			Check(PhdHipLib.phd_map_error(nav, (IntPtr) pt, truth.Count, c, p, (IntPtr) pa, (IntPtr) ph, out length, out times, out ospa, out card, out spatial, out sizes));
+		}
+		double[] t = new double[length], o = new double[length], k = new double[length], s = new double[length];
+		int[]    n = new int[length];
+		if (length > 0) { Marshal.Copy(times, t, 0, length); Marshal.Copy(ospa, o, 0, length); Marshal.Copy(card, k, 0, length); Marshal.Copy(spatial, s, 0, length); Marshal.Copy(sizes, n, 0, length); }
+		var series = new List<Tuple<double, double, double, double, int>>(length);
+		for (int i = 0; i < length; i++) { series.Add(Tuple.Create(t[i], o[i], k[i], s[i], n[i])); }
+		return series;
 	}
 
 	/// <summary>≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531) for a batch of

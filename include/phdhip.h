@@ -316,6 +316,37 @@ int phd_map_history_append(phd_navigator* nav, double time);
 int phd_map_history(phd_navigator* nav, int* length, const double** times, const int32_t** best, const double** best_pose7,
                     const int32_t** counts, const int64_t** offsets, const double** w, const double** mean3, const double** cov9);
 
+/* ---- the map error of every logged map (postanalysis: Plot.MapError, Plot.cs:478-529; Plot.OSPA, :531-581) ---------------
+ * The reference's map-error time series over the map log above, computed where the maps lie: one workgroup per entry, FP64.
+ * (Added without a version bump: hosts detect it by symbol.) For every entry k, in log order:
+ *   1. Map.BestMapEstimate (Map.cs:119-142) of the logged components: J = (int) ExpectedSize picks from the list sorted stably
+ *      by falling weight, every pick re-entering with its weight less one (a component of weight >= 2 is picked twice);
+ *      estimate_size[k] = J. The weights are added in map order wherever a tree sum lies within 1e-9 * max(1, sum) of an integer.
+ *   2. where align_pose7 is given and has_reference[k] is not 0 (NULL: all 1), the alignment of Plot.MapError by the estimated
+ *      and the true pose at the reference time, align_pose7[k][0] and [k][1] (x y z qw qx qy qz): p' = R(dq*)(p - c) + c - dx
+ *      with c the estimated location, exactly as monorfs_amd/host/Ospa.hpp::MapError states it. The poses are the host's input:
+ *      it has the estimated one from phd_trajectories_at and the true one from its record.
+ *   3. Plot.OSPA between truth3 (ntruth points: the visited map) and the moved estimate with C = cutoff and P = order: with
+ *      m <= n the sizes of the two sets, ospa = ((min over assignments of sum min(C, d)^P + C^P (n - m)) / n)^(1/P) and
+ *      cardinality = C ((n - m) / n)^(1/P); a pair costs C^P unless C^P - min(C, d)^P > 1e-5 (Plot.cs:561); an empty smaller
+ *      set gives C for both, 0 when both sets are empty (:539-542).
+ *   4. spatial = (ospa^P - cardinality^P)^(1/P) (:519).
+ * times, ospa, cardinality, spatial, estimate_size: [*length], library-owned, valid until the next call on the handle. Waits
+ * for the device; the state and both logs are left as they are.
+ * One entry handles sets of up to PHD_MAP_ERROR_MAX points each (the kernel keeps both sets and the assignment's row state in
+ * 62 KB of LDS, the columns in registers, four per thread). An entry whose J is larger gets NaN values and the size J, an entry
+ * that stored no components (count -1) NaN values and the size -1; the call then returns PHD_ERR_CAPACITY with all outputs
+ * set, and phd_last_error names the first such entry.
+ * PHD_ERR_BAD_ARGUMENT: the map log is off, a multi-device handle, ntruth < 0 or > PHD_MAP_ERROR_MAX, cutoff <= 0,
+ * order < 1, non-finite truth3 / align_pose7 / cutoff / order. PHD_ERR_GENERIC: an entry's assignment met its loop bound
+ * (possible only with logged records that are no numbers); that entry's values are NaN.                                  */
+#define PHD_MAP_ERROR_MAX 1024
+int phd_map_error(phd_navigator* nav, const double* truth3, int ntruth, double cutoff, double order,
+                  const double* align_pose7,      /* [length][2][7]: estimated, true pose per entry; NULL: no alignment */
+                  const uint8_t* has_reference,   /* [length], or NULL = all 1 when align_pose7 is given                */
+                  int* length, const double** times, const double** ospa, const double** cardinality,
+                  const double** spatial, const int32_t** estimate_size);
+
 /* Stage-level entry points for the unit KATs (the stages behind PHDNavigator's public methods).
  *   phd_stage_run(z, with_alpha)  runs predict -> correct -> prune (-> alpha) on EVERY particle of the handle's state, without
  *                                 the weight normalisation / resampling, and leaves each stage's result on the device:

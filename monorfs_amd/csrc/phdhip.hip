@@ -7,6 +7,8 @@
 #include "phd_kernels.h"
 #include "phd_history.h"
 #include "phd_maplog.h"
+#include "phd_maperror.h"
+#include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
 
 #include <algorithm>
 #include <cstdint>
@@ -192,6 +194,10 @@ struct phd_navigator {
 	DevBuf<double> d_mlrec; DevBuf<MapLogEntry> d_mlentry; DevBuf<long long> d_mlbump;
 	std::vector<double> h_mltimes, h_mlrec, h_mlpose, h_mlw, h_mlm, h_mlc;
 	std::vector<MapLogEntry> h_mlentry; std::vector<int32_t> h_mlbest, h_mlcount; std::vector<int64_t> h_mloff;
+	// phd_map_error (phd_maperror.h): the truth set and the alignment of every entry on the device, the results ([3][mecap] doubles:
+	// ospa | cardinality | spatial; [mecap] sizes and the flag word behind them) and their host mirrors; grown on demand
+	DevBuf<double> d_metruth, d_mealign, d_meout; DevBuf<int> d_mesize; int mecap = 0;
+	std::vector<double> h_mealign, h_meout; std::vector<int32_t> h_mesize;
 	// host mirrors handed out by the getters
 	std::vector<double> h_weights, h_poses, h_mw, h_mm, h_mc, h_alpha, h_setll, h_tmp;
 	std::vector<int32_t> h_src;
@@ -1845,6 +1851,81 @@ int phd_map_history(phd_navigator* nav, int* length, const double** times, const
 	if (cov9) *cov9 = nav->h_mlc.data();
 	if (firstbad >= 0) return nav->fail(PHD_ERR_CAPACITY, "phd_map_history: entry " + std::to_string(firstbad) + " did not fit the log's " + std::to_string(nav->mlog_comps) +
 	                                    " components and holds no records (count -1)");
+	return PHD_OK;
+}
+
+// ---- the map error of every logged map (phd_maperror.h) --------------------------------------------
+static_assert(PHD_MAP_ERROR_MAX == PHD_MAPERR_MAX, "include/phdhip.h states the bound the kernel's LDS plan gives");
+int phd_map_error(phd_navigator* nav, const double* truth3, int ntruth, double cutoff, double order, const double* align_pose7, const uint8_t* has_reference,
+                  int* length, const double** times, const double** ospa, const double** cardinality, const double** spatial, const int32_t** estimate_size)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_map_error");
+	if (nav->mlog_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_error: the map log is off (phd_map_history_enable)");
+	if (!length) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_error: `length`");
+	if (ntruth < 0 || ntruth > PHD_MAP_ERROR_MAX || (ntruth > 0 && !truth3))
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_error: " + std::to_string(ntruth) + " truth points (0 .. PHD_MAP_ERROR_MAX = " + std::to_string(PHD_MAP_ERROR_MAX) + ")");
+	if (!(cutoff > 0) || !(order >= 1) || !std::isfinite(cutoff) || !std::isfinite(order)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_map_error: cutoff > 0 and order >= 1");
+	const int L = nav->mlog_len;
+	FINITE_OR_FAIL(nav, truth3, (size_t) ntruth * 3, "phd_map_error");
+	if (align_pose7) FINITE_OR_FAIL(nav, align_pose7, (size_t) L * 14, "phd_map_error");
+	enter(nav);
+	if (L > nav->mecap || !nav->d_metruth) {
+		const int want = std::max(L, std::max(nav->mecap * 2, 64));
+		nav->mecap = 0;
+		hipError_t e = nav->d_metruth.alloc((size_t) PHD_MAP_ERROR_MAX * 3);
+		if (e == hipSuccess) e = nav->d_mealign.alloc((size_t) want * PHD_MAPERR_ALIGN);
+		if (e == hipSuccess) e = nav->d_meout.alloc((size_t) want * 3);
+		if (e == hipSuccess) e = nav->d_mesize.alloc((size_t) want + 1);
+		if (e != hipSuccess) {
+			(void) hipGetLastError();
+			nav->d_metruth.reset(); nav->d_mealign.reset(); nav->d_meout.reset(); nav->d_mesize.reset();
+			return nav->fail(PHD_ERR_DEVICE, std::string("phd_map_error: buffers for ") + std::to_string(want) + " entries: " + hipGetErrorString(e));
+		}
+		nav->mecap = want;
+	}
+	const int cap = nav->mecap, n1 = std::max(L, 1);
+	nav->h_mealign.assign((size_t) n1 * PHD_MAPERR_ALIGN, 0.0);
+	if (align_pose7) {
+		for (int k = 0; k < L; k++) {
+			if (has_reference && !has_reference[k]) continue;
+			// (has | R[9] | c[3], the estimated location | dx[3]: phd_maperror.h)
+			double* al = &nav->h_mealign[(size_t) k * PHD_MAPERR_ALIGN];
+			const double* est7 = align_pose7 + (size_t) k * 14;
+			al[0] = 1.0;
+			monorfs::MapErrorAlignment(est7, est7 + 7, al + 1, al + 13);
+			for (int i = 0; i < 3; i++) al[10 + i] = est7[i];
+		}
+	}
+	nav->h_meout.assign((size_t) n1 * 3, 0.0); nav->h_mesize.assign((size_t) n1 + 1, 0);
+	int flag = 0;
+	if (L > 0) {
+		// (pageable copies: the call waits for the device anyway, and the host arrays are free when each returns)
+		if (ntruth > 0) HC(hipMemcpyAsync(nav->d_metruth, truth3, (size_t) ntruth * 3 * 8, hipMemcpyHostToDevice, nav->stream));
+		HC(hipMemcpyAsync(nav->d_mealign, nav->h_mealign.data(), (size_t) L * PHD_MAPERR_ALIGN * 8, hipMemcpyHostToDevice, nav->stream));
+		HC(hipMemsetAsync(nav->d_mesize + cap, 0, 4, nav->stream));
+		hipLaunchKernelGGL((k_map_error<MapLogEntry>), dim3(L), dim3(256), 0, nav->stream, (const double*) nav->d_mlrec, (long long) nav->mlog_comps, nav->cap,
+		                   (const MapLogEntry*) nav->d_mlentry, (const double*) nav->d_metruth, ntruth, cutoff, order, (const double*) nav->d_mealign,
+		                   (double*) nav->d_meout, nav->d_meout + cap, nav->d_meout + 2 * (size_t) cap, (int*) nav->d_mesize, nav->d_mesize + cap);
+		HC(hipGetLastError());
+		for (int q = 0; q < 3; q++) HC(hipMemcpyAsync(&nav->h_meout[(size_t) q * L], nav->d_meout + (size_t) q * cap, (size_t) L * 8, hipMemcpyDeviceToHost, nav->stream));
+		HC(hipMemcpyAsync(nav->h_mesize.data(), nav->d_mesize, (size_t) L * 4, hipMemcpyDeviceToHost, nav->stream));
+		HC(hipMemcpyAsync(&flag, nav->d_mesize + cap, 4, hipMemcpyDeviceToHost, nav->stream));
+	}
+	HC(hipStreamSynchronize(nav->stream));
+	*length = L;
+	if (times) *times = nav->h_mltimes.data();
+	if (ospa) *ospa = nav->h_meout.data();
+	if (cardinality) *cardinality = nav->h_meout.data() + L;
+	if (spatial) *spatial = nav->h_meout.data() + 2 * (size_t) L;
+	if (estimate_size) *estimate_size = nav->h_mesize.data();
+	if (flag) return nav->fail(PHD_ERR_GENERIC, "phd_map_error: the assignment of an entry met its bound (records in the log that are no numbers); its values are NaN");
+	for (int k = 0; k < L; k++) {
+		if (nav->h_mesize[k] < 0) return nav->fail(PHD_ERR_CAPACITY, "phd_map_error: entry " + std::to_string(k) + " did not fit the map log and holds no records (count -1); its values are NaN");
+		if (nav->h_mesize[k] > PHD_MAP_ERROR_MAX)
+			return nav->fail(PHD_ERR_CAPACITY, "phd_map_error: entry " + std::to_string(k) + " has an estimate of " + std::to_string(nav->h_mesize[k]) + " landmarks, more than PHD_MAP_ERROR_MAX = " +
+			                 std::to_string(PHD_MAP_ERROR_MAX) + "; its values are NaN");
+	}
 	return PHD_OK;
 }
 

@@ -160,6 +160,27 @@ public:
 		return out;
 	}
 
+	// ≙ Plot.MapError (postanalysis/Plot.cs:478-529) over the map log, on the device (phd_map_error; waits for it): for every
+	// entry the OSPA distance with cut-off C and order P between `truth` (the visited map) and Map.BestMapEstimate of the logged
+	// map, its cardinality and spatial parts and the estimate's size. align: empty, or per entry the estimated and the true pose
+	// at the reference time; hasreference: empty (every entry is aligned) or per entry. Ospa.hpp is the same metric on the host.
+	struct MapErrorEntry {
+		double  Time, Ospa, Cardinality, Spatial;
+		int32_t Size;
+	};
+	std::vector<MapErrorEntry> MapError(const std::vector<std::array<double, 3>>& truth, double C = 1.0, double P = 1.0,
+	                                    const std::vector<std::array<Pose3D, 2>>& align = {}, const std::vector<uint8_t>& hasreference = {})
+	{
+		int L = 0;
+		const double *t = nullptr, *o = nullptr, *c = nullptr, *s = nullptr;
+		const int32_t* n = nullptr;
+		check(phd_map_error(nav_, truth.empty() ? nullptr : truth[0].data(), (int) truth.size(), C, P, align.empty() ? nullptr : align[0][0].data(),
+		                    hasreference.empty() ? nullptr : hasreference.data(), &L, &t, &o, &c, &s, &n));
+		std::vector<MapErrorEntry> out(L);
+		for (int k = 0; k < L; k++) out[k] = {t[k], o[k], c[k], s[k], n[k]};
+		return out;
+	}
+
 	// ≙ static QuasiSetLogLikelihood(measurements, map, pose) (:526-531), for a batch of candidate poses (row f4)
 	std::vector<double> QuasiSetLogLikelihood(const std::vector<PixelRangeMeasurement>& measurements,
 	                                          const std::vector<std::array<double, 3>>& landmarks, const std::vector<Pose3D>& poses)

@@ -268,6 +268,32 @@ class PHDNavigator:
             out.append((t[k], b[k], np.array(x[k * 7:k * 7 + 7]), model))
         return out
 
+    def MapError(self, truth, cutoff=1.0, order=1.0, align=None, allow_missing=False):
+        """≙ Plot.MapError (postanalysis/Plot.cs:478-529) over the map log, on the device (phd_map_error; waits for it): a list of
+        (time, ospa, cardinality, spatial, size), oldest entry first, of the OSPA distance with cut-off `cutoff` and order `order`
+        between `truth` (the visited map, [n][3]) and Map.BestMapEstimate of every logged map; size is the estimate's.
+        align: None, or per entry (estimated pose[7], true pose[7]) at the reference time — an entry whose pair is None is not
+        aligned (the estimate is shorter than the reference time, :500). An entry without records or with an estimate beyond
+        PHD_MAP_ERROR_MAX raises PHDError (status 2); allow_missing=True returns the list with NaN values for it."""
+        truth = np.ascontiguousarray(truth, np.float64).reshape(-1, 3)
+        poses, has = None, None
+        if align is not None:
+            align = list(align)
+            has = np.array([a is not None for a in align], np.uint8)
+            poses = np.ascontiguousarray([np.concatenate([np.asarray(a[0], float), np.asarray(a[1], float)]) if a is not None else
+                                          np.tile([0.0, 0, 0, 1, 0, 0, 0], 2) for a in align], np.float64).reshape(-1, 14)
+            if len(poses) != self.map_history_length:
+                raise ValueError("one (estimated, true) pose pair per entry of the map log")
+        n = C.c_int(0)
+        t, o, c, s, z = dp(), dp(), dp(), dp(), ip()
+        rc = self._lib.phd_map_error(self._h, _ptr(truth) if len(truth) else None, len(truth), float(cutoff), float(order),
+                                     _ptr(poses) if poses is not None and len(poses) else None,
+                                     has.ctypes.data_as(_lib.u8p) if has is not None and len(has) else None,
+                                     C.byref(n), C.byref(t), C.byref(o), C.byref(c), C.byref(s), C.byref(z))
+        if rc != 0 and not (allow_missing and rc == PHD_ERR_CAPACITY and n.value > 0):
+            self._check(rc)
+        return [(t[k], o[k], c[k], s[k], z[k]) for k in range(n.value)]
+
     def QuasiSetLogLikelihood(self, measurements, landmarks, poses):
         """≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531), batched over
         candidate poses (phd_quasi_set_loglik): returns one value per pose."""

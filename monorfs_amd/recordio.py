@@ -313,13 +313,14 @@ def phd_params_from_config(config, measurer=None, **caps):
 
 
 MEMBERS = ("scene.world", "trajectory.out", "odometry.out", "measurements.out", "estimate.out", "maps.out", "tags.out", "config.cfg")
+OPTIONAL_MEMBERS = ("vismaps.out",)   # Simulation.SerializedVisibleMaps (Simulation.cs:211-218), in the format of maps.out; read where a record has it
 
 
 def read_record(path):
     """member name -> text, from the zip of Simulation.SaveToFile or a directory holding its members"""
     out = {}
     if os.path.isdir(path):
-        for name in MEMBERS:
+        for name in MEMBERS + OPTIONAL_MEMBERS:
             f = os.path.join(path, name)
             if os.path.exists(f):
                 with open(f) as fh:
@@ -327,7 +328,7 @@ def read_record(path):
     else:
         with zipfile.ZipFile(path) as z:
             for name in z.namelist():
-                if name in MEMBERS:
+                if name in MEMBERS + OPTIONAL_MEMBERS:
                     out[name] = z.read(name).decode()
     return out
 

@@ -3,7 +3,7 @@
 drives the C# solver with `-i=record` drives PHDNavigator here, and estimate.out / maps.out come back in the same
 format (Simulation.SaveToFile, Simulation.cs:391-488).
 
-    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints] [--posted]
+    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints] [--posted [--map-error]]
     python scripts/replay.py --make DIR [--frames K]      # write a small synthetic record first
 
 The host keeps what the reference keeps managed: the motion noise dt * chol(Q) * N(0, I) per particle and the
@@ -16,7 +16,12 @@ copied by Navigator.UpdateTrajectory, Navigator.cs:258-262), read from the traje
 
 --posted: the whole record is posted to the device without a host wait between the first frame and the last (phd_step_async,
 the map log phd_map_history_* and, for waypoints, the trajectory log); the two files are built afterwards from the logs and are
-the same bytes."""
+the same bytes.
+
+--map-error (with --posted): the map-error time series of the post-analysis (Plot.MapError, postanalysis/Plot.cs:478-529) as well,
+computed on the device over the map log (phd_map_error): maperror.out (OSPA) and spatialmaperror.out (its spatial part), one
+`t value` line per frame in g6, with cut-off 1 and order 1 and without the alignment at a reference time. Truth is the visited
+map of the record's vismaps.out where it has one (visited_map below), else the scene's landmarks."""
 import argparse
 import os
 import sys
@@ -48,6 +53,27 @@ def params_of(rec, particles, maxm):
     if measurer is not None:
         p.measurer[:] = [measurer[0], float(np.float32(measurer[1])), float(np.float32(measurer[2]))] + list(measurer[3:7])
     return p, pose
+
+
+def visited_map(frames):
+    """Plot.VisitedMap (postanalysis/Plot.cs:230-248), the rule of monorfs_amd/host/Ospa.hpp::VisitedMap: the landmarks seen
+    (weight > 0) in any frame so far, each once — a landmark is new when nothing already kept lies within 1e-5 of it.
+    frames: per frame (weights[n], means[n][3]) of the visible landmarks. Returns the kept means, [k][3]."""
+    kept = []
+    for w, m in frames:
+        for wi, x in zip(w, np.asarray(m, float).reshape(-1, 3)):
+            if not wi > 0:
+                continue
+            if not any(np.sqrt(np.sum((c - x) ** 2)) <= 1e-5 for c in kept):
+                kept.append(np.array(x))
+    return np.array(kept).reshape(-1, 3)
+
+
+def truth_of(rec):
+    """what --map-error measures against: the visited map of vismaps.out, or the scene's landmarks"""
+    if "vismaps.out" in rec:
+        return visited_map([(mix[0], mix[1]) for _, mix in rio.map_history_from_descriptor(rec["vismaps.out"])])
+    return np.asarray(rio.scene_from_descriptor(rec["scene.world"])[2], float).reshape(-1, 3)
 
 
 class DeviceSolver:
@@ -103,10 +129,16 @@ class DeviceSolver:
             best = b
         return out
 
+    def map_error(self, truth, cutoff=1.0, order=1.0):
+        """per frame (time, ospa, cardinality, spatial, size) over the map log (phd_map_error)"""
+        return self.nav.MapError(truth, cutoff, order)
 
-def replay(rec, particles, seed, solver_cls, estimate="poses", posted=False):
+
+def replay(rec, particles, seed, solver_cls, estimate="poses", map_error=False, posted=False):
     if estimate not in ("poses", "waypoints"):
         raise ValueError("estimate is 'poses' or 'waypoints'")
+    if map_error and not posted:
+        raise ValueError("map_error needs posted: the metric is computed over the map log on the device")
     frames = frames_of(rec)
     p, pose = params_of(rec, particles, max(len(z) for _, _, z in frames))
     solver = solver_cls(p, pose, particles)
@@ -143,7 +175,12 @@ def replay(rec, particles, seed, solver_cls, estimate="poses", posted=False):
                 trajectory.append((t, est))
                 history.append((t, list(trajectory)))
             maps.append((t, bmap))
-    return {"estimate.out": rio.serialize_trajectories(history), "maps.out": rio.serialize_maps(maps)}
+    out = {"estimate.out": rio.serialize_trajectories(history), "maps.out": rio.serialize_maps(maps)}
+    if map_error:
+        series = solver.map_error(truth_of(rec))
+        out["maperror.out"] = rio.serialize_timed_array([(t, [e[1]]) for (t, _, _), e in zip(frames, series)])
+        out["spatialmaperror.out"] = rio.serialize_timed_array([(t, [e[3]]) for (t, _, _), e in zip(frames, series)])
+    return out
 
 
 def make_synthetic_record(path, frames=12, landmarks=14, seed=3):
@@ -191,13 +228,16 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--estimate", choices=("poses", "waypoints"), default="poses")
     ap.add_argument("--posted", action="store_true", help="post the whole record without a host wait; the files are built from the device's logs")
+    ap.add_argument("--map-error", action="store_true", help="with --posted: maperror.out and spatialmaperror.out from the device's map log")
     a = ap.parse_args()
+    if a.map_error and not a.posted:
+        ap.error("--map-error needs --posted")
     if a.make:
         print("wrote", make_synthetic_record(a.make, a.frames))
         if not a.record:
             return
     rec = rio.read_record(a.record)
-    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate, posted=a.posted)
+    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate, map_error=a.map_error, posted=a.posted)
     if a.out:
         rio.write_record(a.out, dict(rec, **out))
     maps = rio.map_history_from_descriptor(out["maps.out"])
