@@ -65,6 +65,9 @@ public class PhdHipLib
 	                                                              out IntPtr w, out IntPtr mean3, out IntPtr cov9);
 	[DllImport(Lib)] public extern static int    phd_map_error(HandleRef nav, IntPtr truth3, int ntruth, double cutoff, double order, IntPtr alignpose7, IntPtr hasreference,
 	                                                            out int length, out IntPtr times, out IntPtr ospa, out IntPtr cardinality, out IntPtr spatial, out IntPtr estimatesize);
+	[DllImport(Lib)] public extern static int    phd_pose_error(HandleRef nav, int mode, IntPtr truth7, int ntruth, IntPtr slots, int firstentry, int refentry, double slamtime,
+	                                                             out int length, out IntPtr times, out IntPtr location, out IntPtr rotation,
+	                                                             out int odolength, out IntPtr odotimes, out IntPtr odolocation, out IntPtr odorotation);
 }
 
 /// <summary>
@@ -306,6 +309,33 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 		if (length > 0) { Marshal.Copy(times, t, 0, length); Marshal.Copy(ospa, o, 0, length); Marshal.Copy(card, k, 0, length); Marshal.Copy(spatial, s, 0, length); Marshal.Copy(sizes, n, 0, length); }
 		var series = new List<Tuple<double, double, double, double, int>>(length);
 		for (int i = 0; i < length; i++) { series.Add(Tuple.Create(t[i], o[i], k[i], s[i], n[i])); }
+		return series;
+	}
+
+	/// <summary>≙ Plot.LocationError, RotationError, OdoLocationError and OdoRotationError (postanalysis/Plot.cs:293-456) over the
+	/// trajectory log, on the device (phd_pose_error; waits for it), as four TimedValue lists in that order. truth: the true
+	/// state at every entry of the log (a TimedState; only the states are read). mode: 0 HistMode.Timed, 1 Smooth, 2 Filter.
+	/// slots: null (the best particle of the map log) or per entry the slot whose path is the estimate then. The estimates are
+	/// the entries from firstentry on; refentry is Plot.RefTime; slamtime the time of the "SLAM ... on" tag, 0 without one.</summary>
+	public List<Tuple<double, double>>[] DevicePoseError(List<Tuple<double, double[]>> truth, int mode, int[] slots, int firstentry, int refentry, double slamtime)
+	{
+		double[] g7 = new double[7 * truth.Count];
+		for (int i = 0; i < truth.Count; i++) { truth[i].Item2.CopyTo(g7, 7 * i); }
+		int length, odolength; IntPtr times, loc, rot, odotimes, odoloc, odorot;
+		fixed (double* pg = g7) fixed (int* ps = slots) {
+			Check(PhdHipLib.phd_pose_error(nav, mode, (IntPtr) pg, truth.Count, (IntPtr) ps, firstentry, refentry, slamtime,
+			                               out length, out times, out loc, out rot, out odolength, out odotimes, out odoloc, out odorot));
+		}
+		return new List<Tuple<double, double>>[] { ToTimedValue(length, times, loc), ToTimedValue(length, times, rot),
+		                                           ToTimedValue(odolength, odotimes, odoloc), ToTimedValue(odolength, odotimes, odorot) };
+	}
+
+	static List<Tuple<double, double>> ToTimedValue(int length, IntPtr times, IntPtr values)
+	{
+		double[] t = new double[length], v = new double[length];
+		if (length > 0) { Marshal.Copy(times, t, 0, length); Marshal.Copy(values, v, 0, length); }
+		var series = new List<Tuple<double, double>>(length);                 // TimedValue
+		for (int k = 0; k < length; k++) { series.Add(Tuple.Create(t[k], v[k])); }
 		return series;
 	}
 

@@ -8,6 +8,7 @@
 #include "phd_history.h"
 #include "phd_maplog.h"
 #include "phd_maperror.h"
+#include "phd_poseerror.h"
 #include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
 
 #include <algorithm>
@@ -198,6 +199,17 @@ struct phd_navigator {
 	// ospa | cardinality | spatial; [mecap] sizes and the flag word behind them) and their host mirrors; grown on demand
 	DevBuf<double> d_metruth, d_mealign, d_meout; DevBuf<int> d_mesize; int mecap = 0;
 	std::vector<double> h_mealign, h_meout; std::vector<int32_t> h_mesize;
+	// phd_pose_error (phd_poseerror.h). Per trajectory-log entry, written by phd_history_append: the map log's length at that
+	// moment — what slots == NULL resolves the estimates from. They name entries of today's map log if it has been on and not
+	// restarted since the trajectory log's first entry: mlog_epoch counts its restarts (every switch on or off is one), and
+	// hist_mepoch is that count when the first entry was made, -1 if the map log was off then. Epochs only grow, so the first
+	// entry's speaks for all of them, and within one epoch the map log only grows, so no mark lies behind its end.
+	// The truth rows, the slots (or those marks) and the Timed start indices on the device, the results ([4][pecap] doubles:
+	// location | rotation | odometry location | odometry rotation) and the host mirrors handed out; grown on demand
+	int mlog_epoch = 0, hist_mepoch = -1;
+	std::vector<int> h_hmark;
+	DevBuf<double> d_petruth, d_peout; DevBuf<int> d_pesel, d_pestart; int pecap = 0;
+	std::vector<double> h_peout, h_petimes, h_peodotimes; std::vector<int> h_pesel, h_pestart;
 	// host mirrors handed out by the getters
 	std::vector<double> h_weights, h_poses, h_mw, h_mm, h_mc, h_alpha, h_setll, h_tmp;
 	std::vector<int32_t> h_src;
@@ -725,7 +737,7 @@ int materialise(phd_navigator* nav)
 int hist_restart(phd_navigator* nav)
 {
 	nav->hist_len = 0;
-	nav->h_htimes.clear();
+	nav->h_htimes.clear(); nav->h_hmark.clear();
 	if (nav->hist_cap < 1) return PHD_OK;
 	nav->hist_pp ^= 1;
 	hipLaunchKernelGGL(k_hist_identity, dim3((nav->Pcap + 255) / 256), dim3(256), 0, nav->stream, nav->hpend(nav->hist_pp), nav->hpdirty(nav->hist_pp), nav->Pcap);
@@ -737,6 +749,7 @@ int hist_restart(phd_navigator* nav)
 int mlog_restart(phd_navigator* nav)
 {
 	nav->mlog_len = 0;
+	nav->mlog_epoch++;
 	nav->h_mltimes.clear();
 	if (nav->mlog_cap < 1) return PHD_OK;
 	HC(hipMemsetAsync(nav->d_mlbump, 0, 2 * sizeof(long long), nav->stream));
@@ -1656,7 +1669,7 @@ int phd_history_enable(phd_navigator* nav, int capacity)
 	// (kernels of posted steps may still write the buffers that go)
 	HC(hipStreamSynchronize(nav->stream));
 	for (int s = 0; s < phd_navigator::MAXSPLIT - 1; s++) if (nav->aux[s]) HC(hipStreamSynchronize(nav->aux[s]));
-	nav->hist_cap = 0; nav->hist_len = 0; nav->h_htimes.clear();
+	nav->hist_cap = 0; nav->hist_len = 0; nav->h_htimes.clear(); nav->h_hmark.clear();
 	nav->d_hpose.reset(); nav->d_hparent.reset(); nav->d_hdirty.reset(); nav->d_hpend.reset();
 	if (capacity == 0) return PHD_OK;
 	const size_t rows = (size_t) capacity * nav->Pcap;
@@ -1692,6 +1705,8 @@ int phd_history_append(phd_navigator* nav, double time)
 	nav->hist_pp = n;
 	nav->hist_len = k + 1;
 	nav->h_htimes.push_back(time);
+	if (k == 0) nav->hist_mepoch = nav->mlog_cap > 0 ? nav->mlog_epoch : -1;
+	nav->h_hmark.push_back(nav->mlog_len);
 	return PHD_OK;
 }
 
@@ -1773,6 +1788,7 @@ int phd_map_history_enable(phd_navigator* nav, int entries, int64_t components)
 	HC(hipStreamSynchronize(nav->stream));
 	for (int s = 0; s < phd_navigator::MAXSPLIT - 1; s++) if (nav->aux[s]) HC(hipStreamSynchronize(nav->aux[s]));
 	nav->mlog_cap = 0; nav->mlog_len = 0; nav->mlog_comps = 0; nav->h_mltimes.clear();
+	nav->mlog_epoch++;
 	nav->d_mlrec.reset(); nav->d_mlentry.reset(); nav->d_mlbump.reset();
 	if (entries == 0) return PHD_OK;
 	hipError_t e = nav->d_mlrec.alloc((size_t) std::max<int64_t>(components, 1) * MIX_REC);
@@ -1926,6 +1942,94 @@ int phd_map_error(phd_navigator* nav, const double* truth3, int ntruth, double c
 			return nav->fail(PHD_ERR_CAPACITY, "phd_map_error: entry " + std::to_string(k) + " has an estimate of " + std::to_string(nav->h_mesize[k]) + " landmarks, more than PHD_MAP_ERROR_MAX = " +
 			                 std::to_string(PHD_MAP_ERROR_MAX) + "; its values are NaN");
 	}
+	return PHD_OK;
+}
+
+// ---- the pose-error series over the trajectory log (phd_poseerror.h) -------------------------------
+static_assert(PHD_POSE_ERROR_MAX == PHD_POSEERR_MAX, "include/phdhip.h states the bound the kernel's LDS plan gives");
+int phd_pose_error(phd_navigator* nav, int mode, const double* truth7, int ntruth, const int32_t* slots, int first_entry, int ref_entry, double slam_time,
+                   int* length, const double** times, const double** location, const double** rotation,
+                   int* odo_length, const double** odo_times, const double** odo_location, const double** odo_rotation)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_pose_error");
+	if (nav->hist_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: the trajectory log is off (phd_history_enable)");
+	const int L = nav->hist_len;
+	if (L < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: the trajectory log is empty");
+	if (!length || !odo_length) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: `length` and `odo_length`");
+	if (mode < PHD_POSE_ERROR_TIMED || mode > PHD_POSE_ERROR_FILTER) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: mode " + std::to_string(mode) + " (0 timed, 1 smooth, 2 filter)");
+	if (!truth7 || ntruth != L) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: " + std::to_string(ntruth) + " true poses for a log of " + std::to_string(L) + " entries (one per entry)");
+	if (first_entry < 0 || first_entry >= L) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: first_entry " + std::to_string(first_entry) + " of " + std::to_string(L));
+	if (ref_entry < 0) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: ref_entry " + std::to_string(ref_entry) + " (entries count from 0)");
+	if (!std::isfinite(slam_time)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: slam_time is not finite");
+	FINITE_OR_FAIL(nav, truth7, (size_t) L * 7, "phd_pose_error");
+	for (int k = 0; k < L; k++) {
+		const double* q = truth7 + (size_t) k * 7 + 3;
+		if (!(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: the true pose of entry " + std::to_string(k) + " has a quaternion of norm 0");
+	}
+	if (slots) {
+		for (int k = 0; k < L; k++) {
+			if (slots[k] < 0 || slots[k] >= nav->P) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: slot " + std::to_string(slots[k]) + " at entry " + std::to_string(k) + " out of range");
+		}
+	}
+	else {
+		if (nav->mlog_cap < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: slots == NULL needs the map log (phd_map_history_enable)");
+		if (nav->hist_mepoch != nav->mlog_epoch)
+			return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_pose_error: slots == NULL, and the map log was off or has been restarted since the trajectory log's first entry was made");
+	}
+	if (L > PHD_POSE_ERROR_MAX) return nav->fail(PHD_ERR_CAPACITY, "phd_pose_error: a log of " + std::to_string(L) + " entries, more than PHD_POSE_ERROR_MAX = " + std::to_string(PHD_POSE_ERROR_MAX));
+	if (nav->P > PHD_POSEERR_MAX_PARTICLES) return nav->fail(PHD_ERR_CAPACITY, "phd_pose_error: " + std::to_string(nav->P) + " particles, more than the 65536 whose slots the kernel keeps in 16 bits");
+	enter(nav);
+	if (L > nav->pecap) {
+		const int want = std::min(std::max(L, std::max(nav->pecap * 2, 64)), PHD_POSE_ERROR_MAX);
+		nav->pecap = 0;
+		hipError_t e = nav->d_petruth.alloc((size_t) want * 7);
+		if (e == hipSuccess) e = nav->d_peout.alloc((size_t) want * 4);
+		if (e == hipSuccess) e = nav->d_pesel.alloc(want);
+		if (e == hipSuccess) e = nav->d_pestart.alloc(want);
+		if (e != hipSuccess) {
+			(void) hipGetLastError();
+			nav->d_petruth.reset(); nav->d_peout.reset(); nav->d_pesel.reset(); nav->d_pestart.reset();
+			return nav->fail(PHD_ERR_DEVICE, std::string("phd_pose_error: buffers for ") + std::to_string(want) + " entries: " + hipGetErrorString(e));
+		}
+		nav->pecap = want;
+	}
+	const int cap = nav->pecap;
+	// the series' lengths and times: Timed one value per estimate; Smooth by entry; Filter by position behind first_entry
+	const int base = mode == PHD_POSE_ERROR_SMOOTH ? 0 : first_entry;
+	const int n = L - base;
+	const int nodo = mode == PHD_POSE_ERROR_TIMED ? n : 1 + std::max(0, n - PHD_POSEERR_ODO);
+	std::vector<double> t(nav->h_htimes.begin() + base, nav->h_htimes.end()), todo(nodo);
+	for (int j = 0; j < nodo; j++) todo[j] = mode == PHD_POSE_ERROR_TIMED ? t[j] : t[j == 0 ? 0 : j + PHD_POSEERR_ODO - 1];
+	// start_i of Timed mode: the estimates before i whose time lies before slam_time (Plot.cs:360-362)
+	nav->h_pestart.assign(L, 0);
+	for (int i = first_entry + 1; i < L; i++) nav->h_pestart[i] = nav->h_pestart[i - 1] + (nav->h_htimes[i - 1] < slam_time ? 1 : 0);
+	if (slots) nav->h_pesel.assign(slots, slots + L);
+	else nav->h_pesel = nav->h_hmark;
+	std::vector<double> res((size_t) 2 * n + 2 * (size_t) nodo);
+	// (pageable copies: the call waits for the device anyway, and the host arrays are free when each returns)
+	HC(hipMemcpyAsync(nav->d_petruth, truth7, (size_t) L * 7 * 8, hipMemcpyHostToDevice, nav->stream));
+	HC(hipMemcpyAsync(nav->d_pesel, nav->h_pesel.data(), (size_t) L * 4, hipMemcpyHostToDevice, nav->stream));
+	HC(hipMemcpyAsync(nav->d_pestart, nav->h_pestart.data(), (size_t) L * 4, hipMemcpyHostToDevice, nav->stream));
+	const size_t lds = ((size_t) L * sizeof(unsigned short) + 15) & ~(size_t) 15;   // the slot row: at most 48 KB
+	hipLaunchKernelGGL((k_pose_error<MapLogEntry>), dim3(mode == PHD_POSE_ERROR_TIMED ? n : 1), dim3(256), lds, nav->stream, (const double*) nav->d_hpose, (const int*) nav->d_hparent,
+	                   (const int*) nav->d_hdirty, L, nav->P, nav->Pcap, (const double*) nav->d_petruth, (const int*) nav->d_pesel, slots ? 0 : 1,
+	                   (const MapLogEntry*) nav->d_mlentry, nav->mlog_len, (const int*) nav->d_pestart, mode, first_entry, ref_entry, (double*) nav->d_peout, cap);
+	HC(hipGetLastError());
+	for (int q = 0; q < 4; q++) {
+		HC(hipMemcpyAsync(res.data() + (q < 2 ? (size_t) q * n : 2 * (size_t) n + (size_t) (q - 2) * nodo), nav->d_peout + (size_t) q * cap, (size_t) (q < 2 ? n : nodo) * 8,
+		                  hipMemcpyDeviceToHost, nav->stream));
+	}
+	HC(hipStreamSynchronize(nav->stream));
+	nav->h_peout.swap(res); nav->h_petimes.swap(t); nav->h_peodotimes.swap(todo);
+	*length = n;
+	*odo_length = nodo;
+	if (times) *times = nav->h_petimes.data();
+	if (location) *location = nav->h_peout.data();
+	if (rotation) *rotation = nav->h_peout.data() + n;
+	if (odo_times) *odo_times = nav->h_peodotimes.data();
+	if (odo_location) *odo_location = nav->h_peout.data() + 2 * (size_t) n;
+	if (odo_rotation) *odo_rotation = nav->h_peout.data() + 2 * (size_t) n + nodo;
 	return PHD_OK;
 }
 

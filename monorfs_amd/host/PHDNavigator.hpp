@@ -181,6 +181,29 @@ public:
 		return out;
 	}
 
+	// ≙ Plot.LocationError / RotationError / OdoLocationError / OdoRotationError (postanalysis/Plot.cs:293-456) over the
+	// trajectory log, on the device (phd_pose_error; waits for it). truth: the true pose at every entry of the log. mode:
+	// PHD_POSE_ERROR_TIMED / _SMOOTH / _FILTER. slots: per entry the slot whose path is the estimate then; empty: the best
+	// particle of the map log. The estimates are the entries from first_entry on; ref_entry is the entry both paths are taken
+	// relative to (Plot.RefTime); slam_time the time of the "SLAM ... on" tag, 0 without one. PoseError.hpp is the same metric
+	// on the host.
+	struct PoseErrorSeries {
+		std::vector<double> Times, Location, Rotation, OdoTimes, OdoLocation, OdoRotation;
+	};
+	PoseErrorSeries PoseError(const std::vector<Pose3D>& truth, int mode = PHD_POSE_ERROR_TIMED, const std::vector<int32_t>& slots = {},
+	                          int first_entry = 0, int ref_entry = 0, double slam_time = 0.0)
+	{
+		if (!slots.empty() && slots.size() != truth.size()) throw std::invalid_argument("PoseError: one slot per true pose");
+		int n = 0, m = 0;
+		const double *t = nullptr, *a = nullptr, *r = nullptr, *ot = nullptr, *oa = nullptr, *orot = nullptr;
+		check(phd_pose_error(nav_, mode, truth.empty() ? nullptr : truth[0].data(), (int) truth.size(), slots.empty() ? nullptr : slots.data(),
+		                     first_entry, ref_entry, slam_time, &n, &t, &a, &r, &m, &ot, &oa, &orot));
+		PoseErrorSeries out;
+		out.Times.assign(t, t + n); out.Location.assign(a, a + n); out.Rotation.assign(r, r + n);
+		out.OdoTimes.assign(ot, ot + m); out.OdoLocation.assign(oa, oa + m); out.OdoRotation.assign(orot, orot + m);
+		return out;
+	}
+
 	// ≙ static QuasiSetLogLikelihood(measurements, map, pose) (:526-531), for a batch of candidate poses (row f4)
 	std::vector<double> QuasiSetLogLikelihood(const std::vector<PixelRangeMeasurement>& measurements,
 	                                          const std::vector<std::array<double, 3>>& landmarks, const std::vector<Pose3D>& poses)

@@ -294,6 +294,34 @@ class PHDNavigator:
             self._check(rc)
         return [(t[k], o[k], c[k], s[k], z[k]) for k in range(n.value)]
 
+    POSE_ERROR_MODES = {"timed": 0, "smooth": 1, "filter": 2}   # PHD_POSE_ERROR_* (HistMode, postanalysis/Program.cs:68)
+
+    def PoseError(self, truth, mode="timed", slots=None, first_entry=0, ref_entry=0, slam_time=0.0):
+        """≙ Plot.LocationError / RotationError / OdoLocationError / OdoRotationError (postanalysis/Plot.cs:293-456) over the
+        trajectory log, on the device (phd_pose_error; waits for it): (times, location, rotation, odo_times, odo_location,
+        odo_rotation). truth: [L][7], the true pose at every entry of the log. mode: "timed" (per estimate the mean error of its
+        whole path, from the `slam_time` index on), "smooth" (the newest estimate's path, per entry) or "filter" (every
+        estimate's newest pose). slots: per entry the slot whose path is the estimate then; None: the best particle of the map
+        log (the rule of WayPointsAt). The estimates are the entries from first_entry on; ref_entry is the entry both paths are
+        taken relative to (Plot.RefTime). monorfs_amd/host/PoseError.hpp is the same metric on the host."""
+        if mode not in self.POSE_ERROR_MODES:
+            raise ValueError("mode is 'timed', 'smooth' or 'filter'")
+        truth = np.ascontiguousarray(truth, np.float64).reshape(-1, 7)
+        q = None
+        if slots is not None:
+            q = np.ascontiguousarray(list(slots) if not isinstance(slots, np.ndarray) else slots, np.int32).reshape(-1)
+            if len(q) != len(truth):
+                raise ValueError("one slot per true pose (one per entry of the trajectory log)")
+        n, m = C.c_int(0), C.c_int(0)
+        t, a, r, ot, oa, orot = dp(), dp(), dp(), dp(), dp(), dp()
+        self._check(self._lib.phd_pose_error(self._h, self.POSE_ERROR_MODES[mode], _ptr(truth) if len(truth) else None, len(truth),
+                                             q.ctypes.data_as(ip) if q is not None and len(q) else None, int(first_entry), int(ref_entry), float(slam_time),
+                                             C.byref(n), C.byref(t), C.byref(a), C.byref(r), C.byref(m), C.byref(ot), C.byref(oa), C.byref(orot)))
+
+        def arr(p, k):
+            return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0)
+        return (arr(t, n.value), arr(a, n.value), arr(r, n.value), arr(ot, m.value), arr(oa, m.value), arr(orot, m.value))
+
     def QuasiSetLogLikelihood(self, measurements, landmarks, poses):
         """≙ static PHDNavigator.QuasiSetLogLikelihood(measurements, map, pose) (PHDNavigator.cs:526-531), batched over
         candidate poses (phd_quasi_set_loglik): returns one value per pose."""

@@ -3,7 +3,8 @@
 drives the C# solver with `-i=record` drives PHDNavigator here, and estimate.out / maps.out come back in the same
 format (Simulation.SaveToFile, Simulation.cs:391-488).
 
-    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints] [--posted [--map-error]]
+    python scripts/replay.py <record.zip | record dir> [--particles N] [--seed S] [--out DIR] [--estimate poses|waypoints] [--posted [--map-error]
+                             [--pose-error [--history timed|smooth|filter] [--reftime T]]]
     python scripts/replay.py --make DIR [--frames K]      # write a small synthetic record first
 
 The host keeps what the reference keeps managed: the motion noise dt * chol(Q) * N(0, I) per particle and the
@@ -21,7 +22,15 @@ the same bytes.
 --map-error (with --posted): the map-error time series of the post-analysis (Plot.MapError, postanalysis/Plot.cs:478-529) as well,
 computed on the device over the map log (phd_map_error): maperror.out (OSPA) and spatialmaperror.out (its spatial part), one
 `t value` line per frame in g6, with cut-off 1 and order 1 and without the alignment at a reference time. Truth is the visited
-map of the record's vismaps.out where it has one (visited_map below), else the scene's landmarks."""
+map of the record's vismaps.out where it has one (visited_map below), else the scene's landmarks.
+
+--pose-error (with --posted --estimate waypoints): the four pose-error series of the post-analysis (Plot.LocationError,
+RotationError, OdoLocationError, OdoRotationError, postanalysis/Plot.cs:293-456) as well, computed on the device over the trajectory
+log (phd_pose_error): locerror.out, roterror.out, odolocerror.out, odoroterror.out, one `t value` line per value in g6. --history
+is the post-analysis' -H (timed, the default: per frame the mean error of the whole path estimated then; smooth; filter),
+--reftime its -t, turned into an entry by the binary search of Plot.cs:99-101 over the times of the log's entries. The truth is the
+record's trajectory.out behind the scene's start pose for entry 0 (the constructor's waypoint); the time of the "SLAM ... on" tag
+comes from tags.out (Plot.cs:343)."""
 import argparse
 import os
 import sys
@@ -74,6 +83,35 @@ def truth_of(rec):
     if "vismaps.out" in rec:
         return visited_map([(mix[0], mix[1]) for _, mix in rio.map_history_from_descriptor(rec["vismaps.out"])])
     return np.asarray(rio.scene_from_descriptor(rec["scene.world"])[2], float).reshape(-1, 3)
+
+
+def reference_entry(times, reftime):
+    """Plot.RefTime (postanalysis/Plot.cs:99-101): List.BinarySearch for `reftime` among the entries' times — the index it hits, the
+    first entry behind reftime where it hits none, 0 where reftime lies behind every entry"""
+    lo, hi = 0, len(times) - 1
+    while lo <= hi:
+        mid = lo + ((hi - lo) >> 1)
+        if times[mid] == reftime:
+            return mid
+        if times[mid] < reftime:
+            lo = mid + 1
+        else:
+            hi = mid - 1
+    return lo if lo != len(times) else 0
+
+
+def slam_time_of(rec):
+    """the time of the first tag that names SLAM and on, 0 without one (Plot.cs:343-346)"""
+    tags = rio.timed_message_from_descriptor([l for l in rec.get("tags.out", "").split("\n") if l != ""])
+    return next((t for t, message in tags if "SLAM" in message and "on" in message), 0.0)
+
+
+def true_poses_of(rec):
+    """what --pose-error measures against, one pose per entry of the trajectory log: the scene's start pose for entry 0
+    (start_waypoints), then trajectory.out frame by frame. Returns (times[L], poses[L][7])."""
+    traj = rio.timed_array_from_descriptor([l for l in rec["trajectory.out"].split("\n") if l != ""], 7)
+    start = np.asarray(rio.scene_from_descriptor(rec["scene.world"])[0], float)
+    return np.array([0.0] + [t for t, _ in traj]), np.array([start] + [np.asarray(x, float) for _, x in traj]).reshape(-1, 7)
 
 
 class DeviceSolver:
@@ -133,19 +171,30 @@ class DeviceSolver:
         """per frame (time, ospa, cardinality, spatial, size) over the map log (phd_map_error)"""
         return self.nav.MapError(truth, cutoff, order)
 
+    def pose_error(self, truth, mode, ref_entry, slam_time):
+        """(times, location, rotation, odo_times, odo_location, odo_rotation) over the trajectory log (phd_pose_error): the
+        estimate of every frame is the path finish_posted reads for it, the best particle of the map log; entry 0 is
+        start_waypoints' and no frame's"""
+        return self.nav.PoseError(truth, mode=mode, slots=None, first_entry=1, ref_entry=ref_entry, slam_time=slam_time)
 
-def replay(rec, particles, seed, solver_cls, estimate="poses", map_error=False, posted=False):
+
+def replay(rec, particles, seed, solver_cls, estimate="poses", map_error=False, pose_error=None, reftime=0.0, posted=False):
     if estimate not in ("poses", "waypoints"):
         raise ValueError("estimate is 'poses' or 'waypoints'")
     if map_error and not posted:
         raise ValueError("map_error needs posted: the metric is computed over the map log on the device")
+    if pose_error is not None:
+        if pose_error not in ("timed", "smooth", "filter"):
+            raise ValueError("pose_error is None, 'timed', 'smooth' or 'filter'")
+        if not posted or estimate != "waypoints":
+            raise ValueError("pose_error needs posted and estimate='waypoints': the metric is computed over the trajectory log on the device")
     frames = frames_of(rec)
     p, pose = params_of(rec, particles, max(len(z) for _, _, z in frames))
     solver = solver_cls(p, pose, particles)
+    if posted:   # (the map log first: phd_pose_error takes the estimates from it only if it was on when every waypoint was made)
+        solver.start_posted(len(frames), len(frames) * p.max_components)
     if estimate == "waypoints":
         solver.start_waypoints(len(frames) + 1)
-    if posted:
-        solver.start_posted(len(frames), len(frames) * p.max_components)
     rng = np.random.default_rng(seed)
     cfg = config_of(rec)
     chol = np.linalg.cholesky(cfg["MotionCovarianceMultiplier"] * np.array(cfg["MotionCovariance"], float))   # PHDNavigator.cs:257-259
@@ -180,6 +229,16 @@ def replay(rec, particles, seed, solver_cls, estimate="poses", map_error=False, 
         series = solver.map_error(truth_of(rec))
         out["maperror.out"] = rio.serialize_timed_array([(t, [e[1]]) for (t, _, _), e in zip(frames, series)])
         out["spatialmaperror.out"] = rio.serialize_timed_array([(t, [e[3]]) for (t, _, _), e in zip(frames, series)])
+    if pose_error is not None:
+        times, truth = true_poses_of(rec)
+        if len(truth) != len(frames) + 1:
+            raise ValueError("trajectory.out has %d poses for %d frames" % (len(truth) - 1, len(frames)))
+        times[1:] = [t for t, _, _ in frames]   # (the log's times: the frames')
+        t, loc, rot, ot, oloc, orot = solver.pose_error(truth, pose_error, reference_entry(list(times), reftime), slam_time_of(rec))
+        out["locerror.out"] = rio.serialize_timed_array([(a, [b]) for a, b in zip(t, loc)])
+        out["roterror.out"] = rio.serialize_timed_array([(a, [b]) for a, b in zip(t, rot)])
+        out["odolocerror.out"] = rio.serialize_timed_array([(a, [b]) for a, b in zip(ot, oloc)])
+        out["odoroterror.out"] = rio.serialize_timed_array([(a, [b]) for a, b in zip(ot, orot)])
     return out
 
 
@@ -229,15 +288,22 @@ def main():
     ap.add_argument("--estimate", choices=("poses", "waypoints"), default="poses")
     ap.add_argument("--posted", action="store_true", help="post the whole record without a host wait; the files are built from the device's logs")
     ap.add_argument("--map-error", action="store_true", help="with --posted: maperror.out and spatialmaperror.out from the device's map log")
+    ap.add_argument("--pose-error", action="store_true", help="with --posted --estimate waypoints: locerror.out, roterror.out, odolocerror.out and odoroterror.out "
+                                                              "from the device's trajectory log")
+    ap.add_argument("--history", choices=("timed", "smooth", "filter"), default="timed", help="the history mode of --pose-error (postanalysis -H)")
+    ap.add_argument("--reftime", type=float, default=0.0, help="the reference time of --pose-error (postanalysis -t)")
     a = ap.parse_args()
     if a.map_error and not a.posted:
         ap.error("--map-error needs --posted")
+    if a.pose_error and not (a.posted and a.estimate == "waypoints"):
+        ap.error("--pose-error needs --posted --estimate waypoints")
     if a.make:
         print("wrote", make_synthetic_record(a.make, a.frames))
         if not a.record:
             return
     rec = rio.read_record(a.record)
-    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate, map_error=a.map_error, posted=a.posted)
+    out = replay(rec, a.particles, a.seed, DeviceSolver, estimate=a.estimate, map_error=a.map_error, posted=a.posted,
+                 pose_error=a.history if a.pose_error else None, reftime=a.reftime)
     if a.out:
         rio.write_record(a.out, dict(rec, **out))
     maps = rio.map_history_from_descriptor(out["maps.out"])
