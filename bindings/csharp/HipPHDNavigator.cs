@@ -48,6 +48,7 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_update_motion(HandleRef nav, IntPtr odometry6, IntPtr noise6, int nparticles, [MarshalAs(UnmanagedType.U1)] bool perfectstill);
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik_grad(HandleRef nav, IntPtr poses7, int nposes, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, IntPtr result, IntPtr gradients6);
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik(HandleRef nav, IntPtr poses7, int nposes, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, IntPtr result);
+	[DllImport(Lib)] public extern static int    phd_quasi_ascent(HandleRef nav, IntPtr initial6, int nestimates, IntPtr linearpoint7, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, int maxiterations, int rounditerations, IntPtr poses6, IntPtr values, IntPtr iterations, IntPtr hessians36);
 	[DllImport(Lib)] public extern static int    phd_set_depth_map(HandleRef nav, IntPtr depth, int width, int height);
 	[DllImport(Lib)] public extern static int    phd_slam_update(HandleRef nav, IntPtr z3, int nmeasurements, [MarshalAs(UnmanagedType.U1)] bool onlymapping, double uresample);
 	[DllImport(Lib)] public extern static IntPtr phd_weights(HandleRef nav, out int length);
@@ -372,6 +373,37 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 		gradients = new double[poses.Length][];
 		for (int i = 0; i < poses.Length; i++) { gradients[i] = new double[6]; Array.Copy(g, 6 * i, gradients[i], 0, 6); }
 		return result;
+	}
+
+	/// <summary>≙ LoopyPHDNavigator.LogLikeGradientAscent (LoopyPHDNavigator.cs:916-965) for several initial estimates side by
+	/// side, resident on the device (phd_quasi_ascent): one call per maxestimates estimates (at most the handle's max_particles / 16).
+	/// Returns the maxima as linear poses; loglike[a] is the value at poses[a]. An estimate still climbing after maxiterations
+	/// iterations is returned as it stands then and capped is set.</summary>
+	public double[][] DeviceLogLikeGradientAscent(double[][] initial, List<PixelRangeMeasurement> measurements, IMap map, Pose3D linearpoint,
+	                                              int maxestimates, out double[] loglike, out bool capped, int averagemode = 0, int maxiterations = 1000)
+	{
+		const int StatusCapacity = 2;                                     // PHD_ERR_CAPACITY
+		int n = initial.Length;
+		double[] z = new double[3 * measurements.Count], lm = new double[3 * map.Count], p6 = new double[6 * n], lin = linearpoint.State;
+		for (int i = 0; i < measurements.Count; i++) { measurements[i].ToLinear().CopyTo(z, 3 * i); }
+		int j = 0;
+		foreach (Gaussian landmark in map) { landmark.Mean.CopyTo(lm, 3 * j++); }
+		for (int i = 0; i < n; i++) { initial[i].CopyTo(p6, 6 * i); }
+		double[] result = new double[6 * n];
+		int[] iterations = new int[n];
+		loglike = new double[n];
+		capped = false;
+		fixed (double* pz = z) fixed (double* pl = lm) fixed (double* pp = p6) fixed (double* plin = lin) fixed (double* pr = result) fixed (double* pv = loglike) fixed (int* pi = iterations) {
+			for (int s = 0; s < n; s += Math.Max(1, maxestimates)) {
+				int m = Math.Min(Math.Max(1, maxestimates), n - s);
+				int status = PhdHipLib.phd_quasi_ascent(nav, (IntPtr) (pp + 6 * s), m, (IntPtr) plin, (IntPtr) pl, map.Count, (IntPtr) pz, measurements.Count,
+				                                        averagemode, maxiterations, 0, (IntPtr) (pr + 6 * s), (IntPtr) (pv + s), (IntPtr) (pi + s), IntPtr.Zero);
+				if (status == StatusCapacity) { capped = true; } else { Check(status); }
+			}
+		}
+		double[][] poses = new double[n][];
+		for (int i = 0; i < n; i++) { poses[i] = new double[6]; Array.Copy(result, 6 * i, poses[i], 0, 6); }
+		return poses;
 	}
 
 	/// <summary>≙ PHDNavigator.SlamUpdate (PHDNavigator.cs:323-362).</summary>

@@ -124,7 +124,7 @@ phd_navigator* phd_create(const phd_params* params, int device);
  * Available on such a handle: phd_reset, phd_set_poses / _weights / _map, phd_update_motion, phd_slam_update,
  * phd_set_measurements / phd_step_async / phd_sync — phd_step_async only POSTS the step to the workers and returns (a ring
  * of 256 posted steps; nothing of a step waits for the host, what it finds surfaces at phd_sync) —, the getters, phd_upload /
- * download_state_soa, phd_set_frozen / _split / _all_pairs / _association_workspace, phd_quasi_set_loglik[_grad], phd_resample /
+ * download_state_soa, phd_set_frozen / _split / _all_pairs / _association_workspace, phd_quasi_set_loglik[_grad], phd_quasi_ascent, phd_resample /
  * phd_particle_depleted, the timing calls (first shard); the stage-level KAT entry points and the per-rank sharding primitives
  * below return PHD_ERR_BAD_ARGUMENT.                                                                                     */
 phd_navigator* phd_create_multi(const phd_params* params, const int* devices, int ndevices);
@@ -527,6 +527,40 @@ int phd_quasi_set_loglik(phd_navigator* nav, const double* poses7, int nposes, c
  * two under which the reference's own LoopyPHDNavigatorTest.LogLike2D assertion holds; tests/test_oracle_kat.py).     */
 int phd_quasi_set_loglik_grad(phd_navigator* nav, const double* poses7, int nposes, const double* landmarks3, int nlandmarks,
                               const double* z3, int nmeasurements, int average_mode, double* out, double* gradients6);
+
+/* LoopyPHDNavigator.LogLikeGradientAscent (LoopyPHDNavigator.cs:916-965) resident on the device, for nestimates initial
+ * estimates side by side (monorfs_amd/csrc/phd_ascent.h): what monorfs_amd/loopy.py::LogLikeGradientAscent drives from the
+ * host with two batch calls per iteration, as ONE call — one copy in, a chain of kernels, one copy out. Per estimate the
+ * reference's loop: the gradient of phd_quasi_set_loglik_grad at the last TRIED pose, clipped to norm 10, the step 1e-2
+ * halved up to PHD_ASCENT_LINE times until the value of phd_quasi_set_loglik does not decrease, until an iteration gains no
+ * more than 1e-3. The evaluations are the two batch calls' kernels, same bits; an estimate that has stopped is skipped by
+ * every later kernel.
+ * initial6[nestimates][6] linear poses around linearpoint7 (Pose3D.Add), landmarks3 / z3 / average_mode as for the batch
+ * calls. PHD_ASCENT_LINE * nestimates <= max_particles (a line search is one batch): more is PHD_ERR_BAD_ARGUMENT, the
+ * wrappers split the estimates into several calls.
+ * Iterations are enqueued round_iterations at a time (0: the library's default); between two rounds the host reads one
+ * word, the number of estimates still climbing, and stops at zero. The results do not depend on round_iterations.
+ * max_iterations >= 1 bounds the call (the reference's loop has no bound): estimates still climbing then return their state
+ * after exactly max_iterations iterations and the call returns PHD_ERR_CAPACITY with all outputs set.
+ * poses6[nestimates][6], values[nestimates] (the value at poses6), iterations[nestimates] (line searches run).
+ * hessians36: NULL, or [nestimates][6][6] row-major — the rows (g(pose + eps e_i) - g(pose - eps e_i)) / (2 eps), eps =
+ * 1e-5, of LogLikeFitCovariance (:976-1021) at the returned poses, raw: the NaN test, the eigenvalue clip and the
+ * pseudo-inverse stay with the host.
+ * PHD_FLAG_BIG_CLUSTER in any evaluation: PHD_ERR_ASSOCIATION. Non-finite input: PHD_ERR_BAD_ARGUMENT. Synchronous; touches
+ * neither the particle state nor the logs nor the batch calls' buffers; a multi-device handle uses its first shard.       */
+#define PHD_ASCENT_LINE 16
+int phd_quasi_ascent(phd_navigator* nav, const double* initial6, int nestimates, const double* linearpoint7,
+                     const double* landmarks3, int nlandmarks, const double* z3, int nmeasurements,
+                     int average_mode, int max_iterations, int round_iterations,
+                     double* poses6, double* values, int32_t* iterations,
+                     double* hessians36 /* [nestimates][6][6] row-major, or NULL */);
+
+/* Test surface for the control kernels of phd_quasi_ascent: k_ascent_candidates, then k_ascent_select on the caller's
+ * values16[nestimates][16], no evaluation in between, every estimate active. Returns cand6[n][16][6], cand7[n][16][7], the
+ * index of the candidate the line search ended on, the new pose6 / loglike, nextpose7 and the active word.              */
+int phd_test_ascent_control(phd_navigator* nav, const double* pose6, const double* loglike, const double* gradients6, const double* values16,
+                            int nestimates, const double* linearpoint7, double* cand6, double* cand7, int32_t* chosen,
+                            double* newpose6, double* newloglike, double* nextpose7, int32_t* active);
 
 /* Test surface for the assignment enumerators the set log-likelihood runs on the device: MurtyPairing (mode 0,
  * GraphCombinatorics.cs:241-272; n <= 256) or LexicographicalPairing(matrix, modelsize) (mode 1, :280-334; n <= 5) on a

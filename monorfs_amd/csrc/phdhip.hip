@@ -9,6 +9,7 @@
 #include "phd_maplog.h"
 #include "phd_maperror.h"
 #include "phd_poseerror.h"
+#include "phd_ascent.h"
 #include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
 
 #include <algorithm>
@@ -137,6 +138,8 @@ struct phd_navigator {
 	DevBuf<double> d_quasi;       // phd_quasi_set_loglik: poses[Pcap][7], landmarks[Jcap][3], z[256][3], out[Pcap]
 	PinBuf<int>    h_status;      // pinned mirror of [d_sel (two parities) | d_info | d_flags], one block on the device
 	PinBuf<double> h_quasi;       // ... its pinned mirror on the host (+ one word for the flags): one stream wait per call, no pageable copies
+	DevBuf<double> d_ascent;      // phd_quasi_ascent: the inputs, the per-estimate state and the results of one call (ascent_layout), made on first use
+	PinBuf<double> h_ascent;      // ... the pinned mirror of what is copied in and out, and the word the host reads between rounds
 	DevBuf<double> d_gw; int gwcap = 0;              // gathered weights of all ranks (+ their status words behind them: flagslot)
 	DevBuf<double> d_stage;                          // device staging of phd_set_poses / phd_set_weights (stored into the IN bank by k_store_small)
 	// pinned host staging of the per-frame inputs (poses, weights, odometry + noise, measurements): the caller's buffers are
@@ -446,6 +449,8 @@ struct StepVariant {
 	void (*assoc)(DevParams, StepBufs, int);
 	void (*quasi)(DevParams, StepBufs, int);
 	void (*quasi_grad)(DevParams, StepBufs, int);
+	void (*ascent)(DevParams, StepBufs, int, const int*, int);        // the same two bodies for phd_quasi_ascent: workgroups of stopped estimates return
+	void (*ascent_grad)(DevParams, StepBufs, int, const int*, int);
 	int  (*chain_pool)(int);
 	int zi() const { return zb >> 1; }   // index of ZB = 1, 2, 4 (phd_navigator::chain_ok)
 	int chain_lds(int cutcap) const { return chain_pool(cutcap); }
@@ -457,7 +462,7 @@ template <int ZB, bool HALF, bool DEPTH>
 StepVariant make_variant()
 {
 	return {ZB, HALF, DEPTH, k_particle_chain<ZB, HALF, DEPTH>, k_sweep<ZB, HALF, DEPTH>, k_emit_prune<DEPTH>, k_emit_finish<DEPTH>, k_alpha_assoc<ZB, DEPTH>,
-	        k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, chain_lds_bytes<ZB>};
+	        k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, k_ascent_setll<ZB>, k_ascent_setll_grad<ZB>, chain_lds_bytes<ZB>};
 }
 
 const StepVariant step_variants[8] = {make_variant<1, false, false>(), make_variant<1, true, false>(), make_variant<2, false, false>(), make_variant<4, false, false>(),
@@ -990,6 +995,8 @@ phd_navigator* phd_create(const phd_params* params, int device)
 				raise(v.assoc, la);
 				raise(v.quasi, la);
 				raise(v.quasi_grad, la);
+				raise(v.ascent, la);
+				raise(v.ascent_grad, la);
 				lim.alpha[i] = la;
 			}
 			// the one-launch chain: its bodies share one pool, the largest of their layouts, which must fit a workgroup (160 KB)
@@ -1206,6 +1213,198 @@ int phd_quasi_set_loglik_grad(phd_navigator* nav, const double* poses7, int npos
 		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_set_loglik_grad: gradients6 is NULL or average_mode is not 0 / 1");
 	}
 	return quasi_batch(nav, poses7, nposes, landmarks3, nlandmarks, z3, nmeasurements, out, gradients6, average_mode);
+}
+
+// ---- phd_quasi_ascent: LogLikeGradientAscent resident on the device (phd_ascent.h) ----
+namespace {
+
+#define PHD_ASCENT_ROUND 2   // iterations enqueued between two looks at the active count (profiles/ascent_cost.md: searches end after 2 - 5)
+
+// One buffer per handle, in doubles, sized once for the largest call (Pcap / 16 estimates, Jcap landmarks, 256 measurements):
+//   lin[7] | landmarks[J][3] | z[M][3] | head[4] (flag word, slab counter, active count, spare) | pose6[n][6]      <- ONE copy in
+//                                         head[4] | pose6[n][6] | loglike[n] | iterations[n] | hessians[n][36]     <- ONE copy out
+// and behind them the state that never leaves the device. The inputs are packed per call, so `head` moves with J and M.
+struct AscentLayout {
+	size_t lin, lm, z, head, pose6, loglike, iters, hess, out_end, next7, prev, active, chosen, grad, gval, cand6, cand7, values, hpose, hgrad, hval, end;
+};
+
+AscentLayout ascent_layout(size_t n, size_t J, size_t M)
+{
+	AscentLayout l;
+	l.lin = 0; l.lm = 7; l.z = l.lm + J * 3; l.head = l.z + M * 3; l.pose6 = l.head + 4;
+	l.loglike = l.pose6 + n * 6; l.iters = l.loglike + n; l.hess = l.iters + n; l.out_end = l.hess + n * 36;
+	l.next7 = l.out_end; l.prev = l.next7 + n * 7; l.active = l.prev + n; l.chosen = l.active + n; l.grad = l.chosen + n; l.gval = l.grad + n * 6;
+	l.cand6 = l.gval + n; l.cand7 = l.cand6 + n * PHD_ASCENT_LINE * 6; l.values = l.cand7 + n * PHD_ASCENT_LINE * 7;
+	l.hpose = l.values + n * PHD_ASCENT_LINE; l.hgrad = l.hpose + n * 12 * 7; l.hval = l.hgrad + n * 12 * 6; l.end = l.hval + n * 12;
+	return l;
+}
+
+AscentBufs ascent_bufs(double* d, const AscentLayout& l, int n)
+{
+	AscentBufs s;
+	s.n = n; s.lin = d + l.lin;
+	s.flags = (int*) (d + l.head); s.slab = (unsigned long long*) (d + l.head + 1); s.nactive = (int*) (d + l.head + 2);
+	s.pose6 = d + l.pose6; s.loglike = d + l.loglike; s.iterations = (int*) (d + l.iters); s.hess = d + l.hess;
+	s.nextpose7 = d + l.next7; s.prev = d + l.prev; s.active = (int*) (d + l.active); s.chosen = (int*) (d + l.chosen);
+	s.grad = d + l.grad; s.gval = d + l.gval; s.cand6 = d + l.cand6; s.cand7 = d + l.cand7; s.values = d + l.values;
+	s.hpose = d + l.hpose; s.hgrad = d + l.hgrad; s.hval = d + l.hval;
+	return s;
+}
+
+int ascent_ensure(phd_navigator* nav)
+{
+	if (nav->d_ascent && nav->h_ascent) return PHD_OK;
+	const AscentLayout cap = ascent_layout((size_t) (nav->Pcap / PHD_ASCENT_LINE), (size_t) nav->Jcap, 256);
+	HC(nav->d_ascent.alloc(cap.end));
+	HC(nav->h_ascent.alloc(cap.end + 1, hipHostMallocDefault));   // (+ the word read between rounds)
+	return PHD_OK;
+}
+
+// an evaluation launch of the chain: `nposes` poses at `poses7`, values to `setll`, gradients to `qgrad` (NULL: the value kernel)
+int ascent_eval(phd_navigator* nav, const AscentBufs& s, const AscentLayout& l, int J, int M, int average_mode, const double* poses7, int nposes,
+                double* setll, double* qgrad, const int* active, int group)
+{
+	StepBufs b = make_bufs(nav);
+	b.P = nposes; b.M = M; b.z = nav->d_ascent + l.z;
+	b.qposes = poses7; b.qlm = nav->d_ascent + l.lm; b.qJ = J;
+	b.setll = setll; b.qgrad = qgrad; b.qavg = average_mode;
+	b.flags = s.flags; b.bigws_used = s.slab;
+	const StepVariant& v = variant(M, false);
+	hipLaunchKernelGGL(qgrad ? v.ascent_grad : v.ascent, dim3(nposes), dim3(256), (size_t) v.assoc_lds(nav->cutcap), nav->stream, nav->dp, b, nav->cutcap, active, group);
+	HC(hipGetLastError());
+	return PHD_OK;
+}
+
+inline int ascent_blocks(int threads) { return (threads + 255) / 256; }
+
+}  // namespace
+
+int phd_quasi_ascent(phd_navigator* nav, const double* initial6, int nestimates, const double* linearpoint7,
+                     const double* landmarks3, int nlandmarks, const double* z3, int nmeasurements,
+                     int average_mode, int max_iterations, int round_iterations,
+                     double* poses6, double* values, int32_t* iterations, double* hessians36)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);   // as the batch calls: the particle state is not touched
+	const int n = nestimates, J = nlandmarks, M = nmeasurements;
+	if (n < 1 || (long long) n * PHD_ASCENT_LINE > nav->Pcap || J < 0 || J > nav->Jcap || M < 0 || M > nav->prm.max_measurements || M > 256 ||
+	    !initial6 || !linearpoint7 || !poses6 || !values || !iterations || (J && !landmarks3) || (M && !z3)) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_ascent: sizes out of range (16 x estimates <= max_particles, landmarks <= min(1024, max_quantity rounded up to 64), measurements <= max_measurements) or a NULL array");
+	}
+	if (average_mode < 0 || average_mode > 1 || max_iterations < 1 || round_iterations < 0) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_ascent: average_mode is not 0 / 1, max_iterations < 1 or round_iterations < 0");
+	}
+	FINITE_OR_FAIL(nav, initial6, (size_t) n * 6, "phd_quasi_ascent");
+	FINITE_OR_FAIL(nav, linearpoint7, 7, "phd_quasi_ascent");
+	FINITE_OR_FAIL(nav, landmarks3, (size_t) J * 3, "phd_quasi_ascent");
+	FINITE_OR_FAIL(nav, z3, (size_t) M * 3, "phd_quasi_ascent");
+	enter(nav);
+	int rc = ascent_ensure(nav);
+	if (rc) return rc;
+	const AscentLayout l = ascent_layout(n, J, M);
+	double* const d = nav->d_ascent;
+	double* const h = nav->h_ascent;
+	const AscentBufs s = ascent_bufs(d, l, n);
+	std::memcpy(h + l.lin, linearpoint7, 7 * 8);
+	if (J) std::memcpy(h + l.lm, landmarks3, (size_t) J * 3 * 8);
+	if (M) std::memcpy(h + l.z, z3, (size_t) M * 3 * 8);
+	std::memset(h + l.head, 0, 4 * 8);
+	std::memcpy(h + l.pose6, initial6, (size_t) n * 6 * 8);
+	HC(hipMemcpyAsync(d, h, l.loglike * 8, hipMemcpyHostToDevice, nav->stream));
+	hipStream_t st = nav->stream;
+	hipLaunchKernelGGL(k_ascent_begin, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
+	rc = ascent_eval(nav, s, l, J, M, average_mode, s.nextpose7, n, s.gval, s.grad, nullptr, 1);
+	if (rc) return rc;
+	hipLaunchKernelGGL(k_ascent_start, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
+	const int round = round_iterations > 0 ? round_iterations : PHD_ASCENT_ROUND;
+	int* const word = (int*) (h + ascent_layout((size_t) (nav->Pcap / PHD_ASCENT_LINE), (size_t) nav->Jcap, 256).end);
+	int done = 0;
+	while (done < max_iterations) {
+		const int upto = std::min(max_iterations, done + round);
+		for (; done < upto; done++) {
+			if (done > 0) {   // (iteration 0 keeps the first launch's gradient: the same pose through the same kernel)
+				rc = ascent_eval(nav, s, l, J, M, average_mode, s.nextpose7, n, s.gval, s.grad, s.active, 1);
+				if (rc) return rc;
+			}
+			hipLaunchKernelGGL(k_ascent_candidates, dim3(ascent_blocks(n * PHD_ASCENT_LINE)), dim3(256), 0, st, s);
+			rc = ascent_eval(nav, s, l, J, M, average_mode, s.cand7, n * PHD_ASCENT_LINE, s.values, nullptr, s.active, PHD_ASCENT_LINE);
+			if (rc) return rc;
+			hipLaunchKernelGGL(k_ascent_select, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
+		}
+		if (done >= max_iterations) break;   // (the count comes with the results)
+		HC(hipMemcpyAsync(word, s.nactive, 4, hipMemcpyDeviceToHost, st));
+		HC(hipStreamSynchronize(st));
+		if (*word == 0) break;
+	}
+	if (hessians36) {
+		hipLaunchKernelGGL(k_ascent_hess_poses, dim3(ascent_blocks(n * 12)), dim3(256), 0, st, s);
+		rc = ascent_eval(nav, s, l, J, M, average_mode, s.hpose, n * 12, s.hval, s.hgrad, nullptr, 1);
+		if (rc) return rc;
+		hipLaunchKernelGGL(k_ascent_hess_rows, dim3(ascent_blocks(n * 36)), dim3(256), 0, st, s);
+	}
+	HC(hipGetLastError());
+	HC(hipMemcpyAsync(h + l.head, d + l.head, ((hessians36 ? l.out_end : l.hess) - l.head) * 8, hipMemcpyDeviceToHost, st));
+	HC(hipStreamSynchronize(st));
+	std::memcpy(poses6, h + l.pose6, (size_t) n * 6 * 8);
+	std::memcpy(values, h + l.loglike, (size_t) n * 8);
+	std::memcpy(iterations, h + l.iters, (size_t) n * 4);
+	if (hessians36) std::memcpy(hessians36, h + l.hess, (size_t) n * 36 * 8);
+	int flags = 0, nactive = 0;
+	std::memcpy(&flags, h + l.head, 4);
+	std::memcpy(&nactive, h + l.head + 2, 4);
+	if (flags & PHD_FLAG_BIG_CLUSTER) {
+		return nav->fail(PHD_ERR_ASSOCIATION, "phd_quasi_ascent: an association cluster exceeds the on-device solver");
+	}
+	if (nactive > 0) {
+		return nav->fail(PHD_ERR_CAPACITY, "phd_quasi_ascent: estimates were still climbing after max_iterations iterations (their state at the bound is returned)");
+	}
+	return PHD_OK;
+}
+
+int phd_test_ascent_control(phd_navigator* nav, const double* pose6, const double* loglike, const double* gradients6, const double* values16,
+                            int nestimates, const double* linearpoint7, double* cand6, double* cand7, int32_t* chosen,
+                            double* newpose6, double* newloglike, double* nextpose7, int32_t* active)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);
+	const int n = nestimates;
+	if (n < 1 || (long long) n * PHD_ASCENT_LINE > nav->Pcap || !pose6 || !loglike || !gradients6 || !values16 || !linearpoint7 || !cand6 || !cand7 ||
+	    !chosen || !newpose6 || !newloglike || !nextpose7 || !active) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_test_ascent_control: 16 x estimates <= max_particles, no NULL array");
+	}
+	enter(nav);
+	int rc = ascent_ensure(nav);
+	if (rc) return rc;
+	const AscentLayout l = ascent_layout(n, 0, 0);
+	double* const d = nav->d_ascent;
+	const AscentBufs s = ascent_bufs(d, l, n);
+	std::vector<double> head(4, 0.0);
+	std::vector<int32_t> ones(n, 1), zeros(n, 0);
+	std::vector<double> prev(n, -INFINITY);
+	HC(hipStreamSynchronize(nav->stream));
+	HC(hipMemcpy(d + l.lin, linearpoint7, 7 * 8, hipMemcpyHostToDevice));
+	HC(hipMemcpy(d + l.head, head.data(), 4 * 8, hipMemcpyHostToDevice));
+	HC(hipMemcpy(s.pose6, pose6, (size_t) n * 6 * 8, hipMemcpyHostToDevice));
+	HC(hipMemcpy(s.loglike, loglike, (size_t) n * 8, hipMemcpyHostToDevice));
+	HC(hipMemcpy(s.prev, prev.data(), (size_t) n * 8, hipMemcpyHostToDevice));
+	HC(hipMemcpy(s.grad, gradients6, (size_t) n * 6 * 8, hipMemcpyHostToDevice));
+	HC(hipMemcpy(s.active, ones.data(), (size_t) n * 4, hipMemcpyHostToDevice));
+	HC(hipMemcpy(s.iterations, zeros.data(), (size_t) n * 4, hipMemcpyHostToDevice));
+	HC(hipMemset(s.nextpose7, 0, (size_t) n * 7 * 8));
+	hipLaunchKernelGGL(k_ascent_candidates, dim3(ascent_blocks(n * PHD_ASCENT_LINE)), dim3(256), 0, nav->stream, s);
+	HC(hipGetLastError());
+	HC(hipMemcpyAsync(s.values, values16, (size_t) n * PHD_ASCENT_LINE * 8, hipMemcpyHostToDevice, nav->stream));   // (no evaluation in between: the caller's values)
+	hipLaunchKernelGGL(k_ascent_select, dim3(ascent_blocks(n)), dim3(256), 0, nav->stream, s);
+	HC(hipGetLastError());
+	HC(hipStreamSynchronize(nav->stream));
+	HC(hipMemcpy(cand6, s.cand6, (size_t) n * PHD_ASCENT_LINE * 6 * 8, hipMemcpyDeviceToHost));
+	HC(hipMemcpy(cand7, s.cand7, (size_t) n * PHD_ASCENT_LINE * 7 * 8, hipMemcpyDeviceToHost));
+	HC(hipMemcpy(chosen, s.chosen, (size_t) n * 4, hipMemcpyDeviceToHost));
+	HC(hipMemcpy(newpose6, s.pose6, (size_t) n * 6 * 8, hipMemcpyDeviceToHost));
+	HC(hipMemcpy(newloglike, s.loglike, (size_t) n * 8, hipMemcpyDeviceToHost));
+	HC(hipMemcpy(nextpose7, s.nextpose7, (size_t) n * 7 * 8, hipMemcpyDeviceToHost));
+	HC(hipMemcpy(active, s.active, (size_t) n * 4, hipMemcpyDeviceToHost));
+	return PHD_OK;
 }
 
 int phd_test_pairing(phd_navigator* nav, const double* matrix, int n, int mode, int modelsize, int maxcount,

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <stdexcept>
 #include <utility>
 
 namespace monorfs {
@@ -118,12 +119,25 @@ inline Odometry LogLikeGradient(PHDNavigator& nav, const Odometry& pose, const s
 // (`nextvehicle`, :933-934), clipped to GradientClip (Config.cs:95), step GradientAscentRate (Config.cs:94) halved up
 // to 16 times until the value does not decrease, until an iteration gains no more than 1e-3.
 // maxbatch: poses per device call (<= the handle's max_particles). averagemode: see phd_quasi_set_loglik_grad.
+// resident: the same loop as one device call per maxbatch / 16 estimates (PHDNavigator::QuasiAscent, phd_quasi_ascent), with
+// the reference's rate and clip only. maxiterations > 0: every estimate stops after that many iterations (the reference has
+// no bound; 0: none here, ResidentIterationBound on the device, reaching it throws).
+const int ResidentIterationBound = 1000;
 inline std::vector<Odometry> LogLikeGradientAscent(PHDNavigator& nav, const std::vector<Odometry>& initial,
                                                    const std::vector<PixelRangeMeasurement>& measurements,
                                                    const std::vector<std::array<double, 3>>& landmarks, const Pose3D& linearpoint,
                                                    std::vector<double>& loglike, int maxbatch, int averagemode = 0,
-                                                   double gradientascentrate = 1e-2, double gradientclip = 10)
+                                                   double gradientascentrate = 1e-2, double gradientclip = 10,
+                                                   bool resident = false, int maxiterations = 0)
 {
+	if (resident) {
+		if (gradientascentrate != 1e-2 || gradientclip != 10) throw std::invalid_argument("LogLikeGradientAscent: the resident ascent has the reference's rate and clip");
+		PHDNavigator::AscentResult r = nav.QuasiAscent(initial, measurements, landmarks, linearpoint, std::max(1, maxbatch / PHD_ASCENT_LINE), averagemode,
+		                                               maxiterations > 0 ? maxiterations : ResidentIterationBound);
+		if (r.Capped && maxiterations <= 0) throw std::runtime_error("LogLikeGradientAscent: the resident ascent is still climbing at its iteration bound");
+		loglike = r.Values;
+		return r.Poses;
+	}
 	const int n = (int) initial.size();
 	auto values = [&](const std::vector<Pose3D>& poses, std::vector<std::array<double, 6>>* grads) {
 		std::vector<double> out;
@@ -146,7 +160,7 @@ inline std::vector<Odometry> LogLikeGradientAscent(PHDNavigator& nav, const std:
 	std::vector<double> prevvalue(n, -std::numeric_limits<double>::infinity());
 	std::vector<int> active;
 	for (int a = 0; a < n; a++) if (loglike[a] - prevvalue[a] > 1e-3) active.push_back(a);
-	while (!active.empty()) {
+	for (int iteration = 0; !active.empty() && (maxiterations <= 0 || iteration < maxiterations); iteration++) {
 		std::vector<Pose3D> at;
 		for (int a : active) at.push_back(nextpose[a]);
 		values(at, &grad);   // :933-934
@@ -229,6 +243,8 @@ inline void SymEig6(const Matrix6& A, std::array<double, 6>& vals, Matrix6& V)
 }
 }  // namespace detail
 
+inline Matrix6 HessianToCovariance(Matrix6 H);
+
 // ≙ LoopyPHDNavigator.LogLikeFitCovariance (:976-1021): the Hessian of the quasi set log-likelihood at `pose` by central
 // differences (eps = 1e-5) of the analytic gradient — 12 gradient evaluations, one device batch —, NaN -> zero matrix,
 // positive eigenvalues clipped to zero, covariance = pseudo-inverse of the negated result. The reference decomposes
@@ -249,13 +265,18 @@ inline Matrix6 LogLikeFitCovariance(PHDNavigator& nav, const Odometry& pose, con
 	std::vector<std::array<double, 6>> g;
 	nav.QuasiSetLogLikelihood(measurements, landmarks, cand, g, averagemode);
 	Matrix6 H;
-	bool nan = false;
 	for (int i = 0; i < 6; i++) {
-		for (int k = 0; k < 6; k++) {
-			H[i * 6 + k] = (g[2 * i][k] - g[2 * i + 1][k]) / (2 * eps);
-			nan = nan || std::isnan(H[i * 6 + k]);
-		}
+		for (int k = 0; k < 6; k++) H[i * 6 + k] = (g[2 * i][k] - g[2 * i + 1][k]) / (2 * eps);
 	}
+	return HessianToCovariance(H);
+}
+
+// The tail of LogLikeFitCovariance from the raw finite-difference rows on (shared with the resident path, whose rows come from
+// phd_quasi_ascent): NaN -> zero matrix, positive eigenvalues of the symmetric part clipped, pseudo-inverse of the negation
+inline Matrix6 HessianToCovariance(Matrix6 H)
+{
+	bool nan = false;
+	for (double x : H) nan = nan || std::isnan(x);
 	if (nan) H.fill(0.0);
 	Matrix6 S, V;
 	for (int i = 0; i < 6; i++) for (int k = 0; k < 6; k++) S[i * 6 + k] = 0.5 * (H[i * 6 + k] + H[k * 6 + i]);
@@ -275,10 +296,16 @@ inline Matrix6 LogLikeFitCovariance(PHDNavigator& nav, const Odometry& pose, con
 // ≙ LoopyPHDNavigator.FitGaussian (:863-869): mean and covariance of the weight-1 Gaussian fitted near pose0
 inline std::pair<Odometry, Matrix6> FitGaussian(PHDNavigator& nav, const Odometry& pose0, const std::vector<PixelRangeMeasurement>& measurements,
                                                 const std::vector<std::array<double, 3>>& landmarks, const Pose3D& linearpoint,
-                                                int maxbatch, int averagemode = 0)
+                                                int maxbatch, int averagemode = 0, bool resident = false, int maxiterations = 0)
 {
+	if (resident) {   // the ascent and the Hessian rows at its maximum from one device call
+		PHDNavigator::AscentResult r = nav.QuasiAscent({pose0}, measurements, landmarks, linearpoint, 1, averagemode,
+		                                               maxiterations > 0 ? maxiterations : ResidentIterationBound, 0, true);
+		if (r.Capped && maxiterations <= 0) throw std::runtime_error("FitGaussian: the resident ascent is still climbing at its iteration bound");
+		return {r.Poses[0], HessianToCovariance(r.Hessians[0])};
+	}
 	std::vector<double> loglike;
-	const Odometry maxpose = LogLikeGradientAscent(nav, {pose0}, measurements, landmarks, linearpoint, loglike, maxbatch, averagemode)[0];
+	const Odometry maxpose = LogLikeGradientAscent(nav, {pose0}, measurements, landmarks, linearpoint, loglike, maxbatch, averagemode, 1e-2, 10, false, maxiterations)[0];
 	return {maxpose, LogLikeFitCovariance(nav, maxpose, measurements, landmarks, linearpoint, averagemode)};
 }
 
@@ -340,7 +367,8 @@ struct PoseComponent {   // a component of the fitted mixture over linear poses
 // by side, the covariance is fitted once at pose0 (the reference's `maxpose` never moves).
 inline std::vector<PoseComponent> GuidedFitMixture(PHDNavigator& nav, double visionfocal, const Odometry& pose0,
                                                    const std::vector<PixelRangeMeasurement>& measurements, const Map& map,
-                                                   const Pose3D& linearpoint, int maxbatch, double* emptyspace, int averagemode = 0)
+                                                   const Pose3D& linearpoint, int maxbatch, double* emptyspace, int averagemode = 0,
+                                                   bool resident = false, int maxiterations = 0)
 {
 	const Pose3D initpose = PoseAdd(linearpoint, pose0);
 	const std::vector<std::array<double, 3>> jmap = BestMapEstimate(map);
@@ -368,7 +396,7 @@ inline std::vector<PoseComponent> GuidedFitMixture(PHDNavigator& nav, double vis
 	std::vector<PoseComponent> components;
 	if (climbing.empty()) return components;
 	std::vector<double> values;
-	const std::vector<Odometry> poses = LogLikeGradientAscent(nav, climbing, measurements, jmap, linearpoint, values, maxbatch, averagemode);
+	const std::vector<Odometry> poses = LogLikeGradientAscent(nav, climbing, measurements, jmap, linearpoint, values, maxbatch, averagemode, 1e-2, 10, resident, maxiterations);
 	bool havecov = false;
 	Matrix6 localcov{};
 	auto pinvquad = [](const Matrix6& cov, const Odometry& d) {   // d' pinv(cov) d

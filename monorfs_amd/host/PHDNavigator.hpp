@@ -11,7 +11,9 @@
 #pragma once
 #include "../../include/phdhip.h"
 
+#include <algorithm>
 #include <array>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -227,6 +229,37 @@ public:
 		                                landmarks.empty() ? nullptr : landmarks[0].data(), (int) landmarks.size(),
 		                                measurements.empty() ? nullptr : measurements[0].data(), (int) measurements.size(), averagemode,
 		                                out.data(), gradients.empty() ? nullptr : gradients[0].data()));
+		return out;
+	}
+
+	// ≙ LoopyPHDNavigator.LogLikeGradientAscent (LoopyPHDNavigator.cs:916-965) for the initial estimates side by side, resident on
+	// the device (phd_quasi_ascent): one call per maxestimates estimates (<= the handle's max_particles / PHD_ASCENT_LINE).
+	// Capped: an estimate was still climbing after maxiterations iterations (PHD_ERR_CAPACITY; its state at the bound is
+	// returned). Hessians (withhessians): the raw finite-difference rows of LogLikeFitCovariance at the returned poses.
+	struct AscentResult {
+		std::vector<std::array<double, 6>>  Poses;
+		std::vector<double>                 Values;
+		std::vector<int32_t>                Iterations;
+		std::vector<std::array<double, 36>> Hessians;
+		bool                                Capped = false;
+	};
+	AscentResult QuasiAscent(const std::vector<std::array<double, 6>>& initial, const std::vector<PixelRangeMeasurement>& measurements,
+	                         const std::vector<std::array<double, 3>>& landmarks, const Pose3D& linearpoint, int maxestimates,
+	                         int averagemode = 0, int maxiterations = 1000, int rounditerations = 0, bool withhessians = false)
+	{
+		const size_t n = initial.size(), chunk = (size_t) (maxestimates > 0 ? maxestimates : 1);
+		AscentResult out;
+		out.Poses.resize(n); out.Values.resize(n); out.Iterations.resize(n);
+		if (withhessians) out.Hessians.resize(n);
+		for (size_t s = 0; s < n; s += chunk) {
+			const int m = (int) std::min(chunk, n - s);
+			const int rc = phd_quasi_ascent(nav_, initial[s].data(), m, linearpoint.data(), landmarks.empty() ? nullptr : landmarks[0].data(),
+			                                (int) landmarks.size(), measurements.empty() ? nullptr : measurements[0].data(), (int) measurements.size(),
+			                                averagemode, maxiterations, rounditerations, out.Poses[s].data(), &out.Values[s], &out.Iterations[s],
+			                                withhessians ? out.Hessians[s].data() : nullptr);
+			if (rc == PHD_ERR_CAPACITY) out.Capped = true;
+			else check(rc);
+		}
 		return out;
 	}
 

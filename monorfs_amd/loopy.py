@@ -122,16 +122,36 @@ def _values_gradients(nav, measurements, landmarks, poses7, average_mode):
     return out, grad
 
 
-def LogLikeGradientAscent(nav, initial, measurements, landmarks, linearpoint, average_mode=0):
+ResidentIterationBound = 1000   # resident=True without max_iterations: what bounds the device call (reaching it raises)
+
+
+def _resident_ascent(nav, initial, measurements, landmarks, linearpoint, average_mode, max_iterations, hessians=False):
+    """the whole search as device calls (PHDNavigator.QuasiAscent chunks by max_particles // 16). Without max_iterations an
+    estimate still climbing at ResidentIterationBound is an error: the reference's loop has no bound to truncate at."""
+    bound = ResidentIterationBound if max_iterations is None else int(max_iterations)
+    out = nav.QuasiAscent(initial, measurements, landmarks, linearpoint, average_mode, max_iterations=bound, hessians=hessians)
+    if out[3] and max_iterations is None:
+        raise RuntimeError("LogLikeGradientAscent(resident=True): still climbing after %d iterations" % bound)
+    return out
+
+
+def LogLikeGradientAscent(nav, initial, measurements, landmarks, linearpoint, average_mode=0, resident=False, max_iterations=None):
     """≙ LoopyPHDNavigator.LogLikeGradientAscent (:916-965) for one initial estimate [6] or several [n][6] run side by
     side. Returns (pose, loglike) or (poses[n][6], loglikes[n]).
 
     Per estimate, exactly the reference's loop: the analytic gradient at the LAST TRIED pose (`nextvehicle`, :933-934 —
     after a rejected step that is not the current one), clipped to GradientClip, step GradientAscentRate halved up to 16
     times until the value does not decrease (:943-951), until an iteration gains no more than 1e-3. The 16 candidate
-    steps of an iteration are evaluated as one device batch and the first acceptable one is taken."""
+    steps of an iteration are evaluated as one device batch and the first acceptable one is taken.
+
+    resident=True: the same loop as ONE device call per max_particles // 16 estimates (nav.QuasiAscent, phd_quasi_ascent);
+    the host sees neither gradients nor candidates. max_iterations: stop every estimate after that many iterations (the
+    reference has no bound; None: none here, ResidentIterationBound on the device)."""
     initial = np.asarray(initial, float)
     single = initial.ndim == 1
+    if resident:
+        pose, loglike = _resident_ascent(nav, initial.reshape(-1, OdoSize), measurements, landmarks, linearpoint, average_mode, max_iterations)[:2]
+        return (pose[0], loglike[0]) if single else (pose, loglike)
     pose = initial.reshape(-1, OdoSize).copy()
     n = len(pose)
     lin = np.asarray(linearpoint, float)
@@ -139,7 +159,9 @@ def LogLikeGradientAscent(nav, initial, measurements, landmarks, linearpoint, av
     loglike, _ = _values_gradients(nav, measurements, landmarks, nextpose7, average_mode)   # :928-929
     prevvalue = np.full(n, -np.inf)
     active = [a for a in range(n) if loglike[a] - prevvalue[a] > 1e-3]
-    while active:
+    iteration = 0
+    while active and (max_iterations is None or iteration < max_iterations):
+        iteration += 1
         _, grad = _values_gradients(nav, measurements, landmarks, nextpose7[active], average_mode)   # :933-934
         cand6 = np.empty((len(active), 16, OdoSize))
         for u, a in enumerate(active):
@@ -191,7 +213,13 @@ def LogLikeFitCovariance(nav, pose, measurements, landmarks, linearpoint, averag
             cand[i, s] = pose3d_add(lin, d)
     _, g = _values_gradients(nav, measurements, landmarks, cand.reshape(-1, 7), average_mode)
     g = g.reshape(OdoSize, 2, OdoSize)
-    hessian = (g[:, 0] - g[:, 1]) / (2 * eps)
+    return HessianToCovariance((g[:, 0] - g[:, 1]) / (2 * eps))
+
+
+def HessianToCovariance(hessian):
+    """The tail of LogLikeFitCovariance (:1003-1021) from the raw finite-difference rows on: NaN -> zero matrix, positive
+    eigenvalues of the symmetric part clipped to zero, pinv(-Hessian). Shared by the host-driven and the resident path."""
+    hessian = np.asarray(hessian, float).reshape(OdoSize, OdoSize)
     if np.isnan(hessian).any():
         hessian = np.zeros((OdoSize, OdoSize))
     vals, vecs = np.linalg.eigh(0.5 * (hessian + hessian.T))
@@ -199,9 +227,14 @@ def LogLikeFitCovariance(nav, pose, measurements, landmarks, linearpoint, averag
     return np.linalg.pinv(-hessian)
 
 
-def FitGaussian(nav, pose0, measurements, landmarks, linearpoint, average_mode=0):
-    """≙ LoopyPHDNavigator.FitGaussian (:863-869): (mean, covariance) of weight 1"""
-    maxpose, _ = LogLikeGradientAscent(nav, pose0, measurements, landmarks, linearpoint, average_mode)
+def FitGaussian(nav, pose0, measurements, landmarks, linearpoint, average_mode=0, resident=False, max_iterations=None):
+    """≙ LoopyPHDNavigator.FitGaussian (:863-869): (mean, covariance) of weight 1. resident=True: the ascent and the Hessian
+    rows at its maximum come from one device call (nav.QuasiAscent)."""
+    if resident:
+        pose, _, _, _, hess = _resident_ascent(nav, np.asarray(pose0, float).reshape(1, OdoSize), measurements, landmarks, linearpoint, average_mode,
+                                               max_iterations, hessians=True)
+        return pose[0], HessianToCovariance(hess[0])
+    maxpose, _ = LogLikeGradientAscent(nav, pose0, measurements, landmarks, linearpoint, average_mode, max_iterations=max_iterations)
     return maxpose, LogLikeFitCovariance(nav, maxpose, measurements, landmarks, linearpoint, average_mode)
 
 
@@ -212,7 +245,7 @@ def _pseudo_determinant(m):
     return float(np.prod(nz)) if len(nz) else 0.0
 
 
-def GuidedFitMixture(nav, pose0, measurements, model, linearpoint, average_mode=0):
+def GuidedFitMixture(nav, pose0, measurements, model, linearpoint, average_mode=0, resident=False, max_iterations=None):
     """≙ LoopyPHDNavigator.GuidedFitMixture (:777-852). `model` = (w, mean, cov) of the map. Returns
     (emptyspace, [(weight, mean[6], cov[6][6]), ...]).
 
@@ -220,7 +253,8 @@ def GuidedFitMixture(nav, pose0, measurements, model, linearpoint, average_mode=
     that explains the pair if it lies within 0.5 of the initial pose (:790-798); a guess worse than a pose far from
     everything is dropped (:821-823); each remaining guess climbs (all of them side by side here); a maximum within
     Mahalanobis 0.1 of an earlier component is dropped (:827-837); the covariance is fitted at `maxpose`, which the
-    reference never updates from pose0 (:800, :839), so it is computed once."""
+    reference never updates from pose0 (:800, :839), so it is computed once. resident / max_iterations: as for
+    LogLikeGradientAscent, for the climb of the guesses."""
     pose0 = np.asarray(pose0, float).reshape(OdoSize)
     lin = np.asarray(linearpoint, float)
     z = np.asarray(measurements, float).reshape(-1, 3)
@@ -241,7 +275,7 @@ def GuidedFitMixture(nav, pose0, measurements, model, linearpoint, average_mode=
     components = []
     if not climbing:
         return emptyspace, components
-    poses, values = LogLikeGradientAscent(nav, np.array(climbing), z, jmap, lin, average_mode)
+    poses, values = LogLikeGradientAscent(nav, np.array(climbing), z, jmap, lin, average_mode, resident, max_iterations)
     localcov = None
     for localpose, localmax in zip(poses, values):
         counted = False

@@ -345,6 +345,37 @@ class PHDNavigator:
                                                         _ptr(z) if len(z) else None, len(z), int(average_mode), _ptr(out), _ptr(grad)))
         return out, grad
 
+    ASCENT_LINE = 16   # PHD_ASCENT_LINE: a call serves max_particles // 16 estimates
+
+    def QuasiAscent(self, initial, measurements, landmarks, linearpoint, average_mode=0, max_iterations=1000, round_iterations=0,
+                    hessians=False):
+        """≙ LoopyPHDNavigator.LogLikeGradientAscent (LoopyPHDNavigator.cs:916-965) for the initial estimates [n][6] side by
+        side, resident on the device (phd_quasi_ascent): returns (poses[n][6], values[n], iterations[n], capped) and, with
+        hessians=True, the raw finite-difference Hessian rows [n][6][6] of LogLikeFitCovariance at the returned poses behind
+        them. More than max_particles // 16 estimates go as several calls. capped: some estimate was still climbing after
+        max_iterations iterations (PHD_ERR_CAPACITY; its state at the bound is what is returned).
+        round_iterations: iterations enqueued between two looks at the active count, 0 the library's default."""
+        z = np.ascontiguousarray(measurements, np.float64).reshape(-1, 3)
+        lm = np.ascontiguousarray(landmarks, np.float64).reshape(-1, 3)
+        lin = np.ascontiguousarray(linearpoint, np.float64).reshape(7)
+        initial = np.ascontiguousarray(initial, np.float64).reshape(-1, 6)
+        n = len(initial)
+        poses, values, iters = np.zeros((n, 6)), np.zeros(n), np.zeros(n, np.int32)
+        hess = np.zeros((n, 6, 6)) if hessians else None
+        chunk = max(1, self.params.max_particles // self.ASCENT_LINE)
+        capped = False
+        for s in range(0, n, chunk):
+            e = min(n, s + chunk)
+            rc = self._lib.phd_quasi_ascent(self._h, _ptr(initial[s:e]), e - s, _ptr(lin), _ptr(lm) if len(lm) else None, len(lm),
+                                            _ptr(z) if len(z) else None, len(z), int(average_mode), int(max_iterations), int(round_iterations),
+                                            _ptr(poses[s:e]), _ptr(values[s:e]), iters[s:e].ctypes.data_as(ip),
+                                            _ptr(hess[s:e]) if hessians else None)
+            if rc == PHD_ERR_CAPACITY:
+                capped = True
+            else:
+                self._check(rc)
+        return (poses, values, iters, capped, hess) if hessians else (poses, values, iters, capped)
+
     def LogLikeGradient(self, pose, measurements, landmarks, linearpoint):
         """≙ LoopyPHDNavigator.LogLikeGradient (LoopyPHDNavigator.cs:876-909): central differences (eps = 1e-5) of the
         quasi set log-likelihood at linearpoint.Add(pose +- eps e_i) — the 12 evaluations go to the device as one batch.
