@@ -109,7 +109,8 @@ void phd_default_params(phd_params* p, int max_particles, int max_components, in
 
 /* ≙ `new PHDNavigator(vehicle, particlecount, onlymapping)` (PHDNavigator.cs:192-208) and
  * ISAM2Lib.newnavigator (ISAM2Navigator.cs:603). `device` is the HIP ordinal. NULL on failure;
- * phd_create_error() then holds the reason.                                                     */
+ * phd_create_error() then holds the reason. max_quantity: up to the LDS bound, about 3400 (one
+ * particle's prune keeps its working set in a workgroup's LDS; every row up to there is pruned).  */
 phd_navigator* phd_create(const phd_params* params, int device);
 /* The same over several devices of one node (SURVEY §8b "device list", §8e): ONE handle, ONE caller thread — what a C# host
  * can drive (Simulation.Update runs the solver from one thread, Simulation.cs:636-673; it has no RCCL). The particles are

@@ -54,8 +54,8 @@ __host__ __device__ inline PruneLds prune_lds(int cutcap)
 	l.NS    = NS;
 	l.rad2  = 0;
 	l.x     = l.rad2 + ((cc / 2 + 1) & ~1);   // (rad2: cc float32) sort words u64[NS]  |  the lists of the pair search (see `rest`)
-	// nbr u64[2*cc], cand float4[cc], owner int[cc], cstart u16[NB+2], absb int[64], ord u16[cc], rowpos u16[cc]
-	int rest  = 2 * cc + 2 * cc + cc / 2 + (PRUNE_NB + 2) / 4 + 1 + 32 + 2 * (cc / 4 + 1) + 4;
+	// nbr u64[2*cc], cand float4[cc], owner int[cc], cstart u16[NB+2], absb u64[64], ord u16[cc], rowpos u16[cc]
+	int rest  = 2 * cc + 2 * cc + cc / 2 + (PRUNE_NB + 2) / 4 + 1 + 64 + 2 * (cc / 4 + 1) + 4;
 	int need  = NS > rest ? NS : rest;
 	const int ranked = NS + 516 + (NS * 2) / 3 + 2;   // what the ranked ordering takes with its canonical indices in LDS (prune_merge_body, haveki)
 	if (ranked > need) need = ranked;
@@ -213,7 +213,7 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 	int*    owner = (int*) (cand + cc);                    // [cut] row that absorbed k (-1: none); the row's bucket while the grid is built
 	unsigned int* cw = (unsigned int*) (owner + cc);       // [(NB + 2) / 2] two 16-bit bucket boundaries per word
 	const unsigned short* cstart = (const unsigned short*) cw;   // [NB + 2] bucket b is [cstart[b], cstart[b + 1])
-	int*    absb  = (int*) (cw + (PRUNE_NB + 2) / 2 + 1);  // [64] absorbed bits as left by the resolving wave
+	unsigned long long* absb = (unsigned long long*) (cw + (PRUNE_NB + 2) / 2 + 1);   // [64] absorbed bits as left by the resolving wave
 	unsigned short* ord = (unsigned short*) (absb + 64);   // [cut] rows in the order the pair search takes them
 	unsigned short* rowpos = ord + cc;                      // [cut] position of row r in `cand`
 	int*    scan  = (int*) (smem + lay.scan);              // [264]
@@ -996,8 +996,12 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 
 	PHD_STAMP(3);
 	// ---- C. who survives: sequential in rank order, one wave, absorbed bits in registers
+	auto readlane64 = [](unsigned long long v, int l) {   // (l wave-uniform)
+		return ((unsigned long long) (unsigned int) __builtin_amdgcn_readlane((int) (v >> 32), l) << 32) | (unsigned int) __builtin_amdgcn_readlane((int) (unsigned int) v, l);
+	};
 	if (wv == 0) {
-		unsigned int absorbed = 0;                  // bit s of lane l <-> row s*64 + l
+		// (64 slots of 64 rows: every cut phd_create admits — the LDS bounds MaxQuantity to some 3400 rows, prune_lds)
+		unsigned long long absorbed = 0;            // bit s of lane l <-> row s*64 + l
 		const int nslots = (cut + 63) >> 6;
 		for (int base = 0; base < cut; base += 64) {
 			const int s0 = base >> 6;
@@ -1012,8 +1016,7 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 				const int l = __ffsll((long long) todo) - 1;
 				todo &= todo - 1;
 				const int i = base + l;
-				unsigned int om = (unsigned int) __builtin_amdgcn_readlane((int) absorbed, l);
-				if ((om >> s0) & 1u) continue;
+				if ((readlane64(absorbed, l) >> s0) & 1ull) continue;
 				const unsigned int w0 = (unsigned int) __builtin_amdgcn_readlane(lolo, l);
 				const int cnt = (int) (w0 & 0xffff);
 				if (cnt <= PRUNE_NBR) {
@@ -1022,9 +1025,8 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 					                              (unsigned int) __builtin_amdgcn_readlane(hilo, l);
 					for (int c = 0; c < cnt; c++) {
 						int k = (int) (((c < 3) ? (lo >> (16 * (c + 1))) : (hi >> (16 * (c - 3)))) & 0xffff);
-						unsigned int km = (unsigned int) __builtin_amdgcn_readlane((int) absorbed, k & 63);
-						if (!((km >> (k >> 6)) & 1u)) {
-							if (lane == (k & 63)) absorbed |= 1u << (k >> 6);
+						if (!((readlane64(absorbed, k & 63) >> (k >> 6)) & 1ull)) {
+							if (lane == (k & 63)) absorbed |= 1ull << (k >> 6);
 							if (lane == 0) owner[k] = i;
 						}
 					}
@@ -1037,11 +1039,11 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 					const double m0 = mm[0], m1 = mm[1], m2 = mm[2];
 					for (int s = i >> 6; s < nslots; s++) {
 						int k = s * 64 + lane;
-						if (k > i && k < cut && !((absorbed >> s) & 1u)) {
+						if (k > i && k < cut && !((absorbed >> s) & 1ull)) {
 							double k0, k1, k2;
 							slab_mean(k, k0, k1, k2);
 							if (quad_sym(Pi, m0 - k0, m1 - k1, m2 - k2) < merge_thr2) {
-								absorbed |= 1u << s;
+								absorbed |= 1ull << s;
 								owner[k] = i;
 							}
 						}
@@ -1049,7 +1051,7 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 				}
 			}
 		}
-		absb[lane] = (int) absorbed;
+		absb[lane] = absorbed;
 	}
 	__syncthreads();
 
@@ -1068,7 +1070,7 @@ __device__ __forceinline__ void prune_merge_body(const DevParams& prm, const Ste
 	// scan[chunk][wave]; a survivor's position is the survivors of the chunks before its own, of the waves before its own in
 	// the chunk, and of the lanes before its own in the wave
 	const int nchunks = (cut + 255) >> 8;   // (at most 14: MaxQuantity is bounded by the LDS, phd_create)
-	auto survives = [&](int i) { return i < cut && !(((unsigned int) absb[i & 63] >> (i >> 6)) & 1u); };
+	auto survives = [&](int i) { return i < cut && !((absb[i & 63] >> (i >> 6)) & 1ull); };
 	for (int q = 0; q < nchunks; q++) {
 		const unsigned long long bal = ballot64(survives(q * 256 + tid));
 		if (lane == 0) scan[q * 4 + wv] = __popcll(bal);

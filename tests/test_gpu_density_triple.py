@@ -206,9 +206,10 @@ def test_corrected_map_longer_than_the_list(nav_mod, monkeypatch):
     detection updates that weigh in the corrected density at the landmarks — without the uncovered entries behind the first
     window the oracle's alpha moves by more than a thousand times the tolerance, which is asserted.
 
-    What the case stays clear of: a cut of more than 2048 rows in k_prune_merge loses row k + 2048 with every absorbed row k (its
-    absorbed flags are one 32-bit word per lane; to be fixed on its own). No row below (rows - 2048) is absorbed here, asserted
-    from the oracle's corrected and pruned maps, so the pruned map is the oracle's and the density sums are what is tested."""
+    What the case stayed clear of when it was written: a cut of more than 2048 rows in k_prune_merge lost row k + 2048 with every
+    absorbed row k (its absorbed flags were one 32-bit word per lane). That limit is gone — the flags are 64 bits per lane, every
+    row phd_create admits, held by tests/test_gpu_prune_paths.py. No row below (rows - 2048) is absorbed here, still asserted
+    from the oracle's corrected and pruned maps: the density sums are what is tested."""
     f, p, mixes, corrected = _long_map_case(88, 32, 24, 100.0, FAR_COV_LONG, NLIGHT_LONG, 3e-7, 7600)
     alpha, setll, Js = _reference(p, f, mixes)
     assert Js == [88] * f.P, Js
