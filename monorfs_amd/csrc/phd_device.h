@@ -496,6 +496,18 @@ __device__ __forceinline__ unsigned long long lanemask_lt()
 	return (1ull << lane_id()) - 1ull;
 }
 
+// inclusive prefix sum over the wave's lanes: lane l gets v of lanes 0 .. l
+__device__ __forceinline__ int wave_incl_scan(int v)
+{
+	const int lane = lane_id();
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) {
+		const int y = __shfl_up(v, o, 64);
+		if (lane >= o) v += y;
+	}
+	return v;
+}
+
 // A value that is the same in every lane (a particle's pose, its rotation matrix), moved to scalar registers: it then
 // costs no vector registers for the rest of the kernel.
 __device__ __forceinline__ double uniform_d(double v)

@@ -466,3 +466,108 @@ def built(name):
     for x in (case.w, case.mean, case.cov) + ref[:3]:
         x.setflags(write=False)
     return case, ref
+
+
+# ---- phase A: which ordering the weights of a map take -------------------------------------------------------------------------
+# The branches of prune_order (phd_prune.h), decided from the weights alone: the bins are weight_bin_of_bits (phd_device.h)
+# restated, NS and capN are PruneLds's, 512 is the most entries the ranked ordering ranks inside one bin.
+def weight_bins(w, min_weight):
+    """exponent and five mantissa bits of a positive double, counted from MinWeight's own bin up, clamped to 1024 bins"""
+    k = (np.asarray(w, np.float64).view(np.uint64) << np.uint64(1)) >> np.uint64(48)
+    base = (np.array([min_weight], np.float64).view(np.uint64) << np.uint64(1)) >> np.uint64(48)
+    return np.clip(k.astype(np.int64) - int(base[0]), 0, 1023)
+
+
+def order_branch(w, max_quantity, min_weight=MIN_WEIGHT):
+    """(branch, ne, sort width): 'registers', 'ranked', 'ranked-rounds', 'one-pass', 'passes' or 'passes-refill'"""
+    w = np.asarray(w, np.float64)
+    w = w[w >= min_weight]                  # what the correction step emits
+    ne, cut = len(w), min(int(max_quantity), len(w))
+    NS = 512
+    while NS < 2 * int(max_quantity):
+        NS *= 2
+    capN = (NS * 2) // 3
+    n = 256
+    while n < ne and n < NS:
+        n *= 2
+    if ne > 256 and cut > 0:
+        counts = np.bincount(weight_bins(w, min_weight), minlength=1024)[::-1]     # from the top bin down
+        above = np.cumsum(counts)
+        t = int(np.argmax(above >= cut))                                           # the threshold bin
+        cnt, crowd = int(above[t]), int(counts[:t + 1].max())
+        if cnt <= capN and crowd <= 512:
+            return ("ranked" if ne <= 2048 else "ranked-rounds"), ne, 0
+        if ne > 1024 and cnt <= NS:
+            n = 256
+            while n < cnt:
+                n *= 2
+            return "one-pass", ne, n
+    if ne <= 256:
+        return "registers", ne, n
+    return ("passes" if ne <= n else "passes-refill"), ne, n
+
+
+def run_deciders(w, max_quantity, min_weight=MIN_WEIGHT):
+    """how the order of the neighbours among the kept rows is decided where the sort words (prune_pack32: 32 - sbits key bits,
+    then the slot) agree in the key: 'lds' (the 32 weight bits behind the key), 'weight' (the full weight) or 'index' (bit-equal
+    weights: the canonical index) — the set of those that occur"""
+    w = np.asarray(w, np.float64)
+    w = w[w >= min_weight]
+    ne, cut = len(w), min(int(max_quantity), len(w))
+    sbits = 1
+    while (1 << sbits) < ne:
+        sbits += 1
+    kept = w[np.argsort(-w, kind="stable")][:cut]
+    body = kept.view(np.uint64) << np.uint64(1)
+    key = body >> np.uint64(64 - (32 - sbits))
+    nxt = ((body << np.uint64(32 - sbits)) >> np.uint64(32))
+    same = key[1:] == key[:-1]
+    kinds = set()
+    if np.any(same & (nxt[1:] != nxt[:-1])):
+        kinds.add("lds")
+    if np.any(same & (nxt[1:] == nxt[:-1]) & (kept[1:] != kept[:-1])):
+        kinds.add("weight")
+    if np.any(kept[1:] == kept[:-1]):
+        kinds.add("index")
+    return kinds
+
+
+def far_apart(w, max_quantity):
+    """the weights on a plane grid 5 m wide (covariance 0.01 I): nothing merges, PruneModel's output is the sorted cut itself"""
+    n = len(w)
+    side = int(np.ceil(np.sqrt(n)))
+    gx, gy = np.meshgrid(np.arange(side) * 5.0, np.arange(side) * 5.0)
+    return Case(w, np.column_stack([gx.ravel()[:n], gy.ravel()[:n], np.zeros(n)]), iso(n), max_quantity)
+
+
+def one_bin(rng, n, lo=1.0):
+    """n distinct weights in one histogram bin, [lo, lo (1 + 1 / 32)), shuffled"""
+    return lo * (1.0 + rng.permutation(n) * (1.0 / 32 / (n + 1)))
+
+
+def with_ties(rng, w):
+    """the three heaviest weights once more: one bit-equal, one a unit in the last place lighter — the full weight and the
+    canonical index decide between neighbours — and the whole shuffled"""
+    top = np.sort(w)[-3:]
+    w = np.concatenate([w, top, np.nextafter(top, 0.0)])
+    return w[rng.permutation(len(w))]
+
+
+def order_case(name):
+    """(case, branch its weights take, run deciders that must occur): the smallest maps that reach each branch of phase A"""
+    rng = np.random.default_rng(sum(name.encode()))
+    if name in ("registers-256", "ranked-257", "ranked-2048", "ranked-rounds-2049"):
+        n = int(name.rsplit("-", 1)[1])
+        w = weights(rng, n - 6)
+        return far_apart(with_ties(rng, w), 600), name.rsplit("-", 1)[0], set()
+    if name == "one-pass":        # 400 in the threshold bin (more than capN = 341, no more than NS = 512), 700 lighter
+        w = np.concatenate([one_bin(rng, 394), weights(rng, 700, 0.01, 0.9)])
+        return far_apart(with_ties(rng, w), 40), "one-pass", {"lds", "weight", "index"}
+    if name == "passes":          # 400 in one bin: ranked refused, one pass of 512
+        return far_apart(with_ties(rng, one_bin(rng, 394)), 40), "passes", {"lds", "weight", "index"}
+    if name == "passes-refill":   # 600 in one bin: more than the sort width, the worse half refilled
+        return far_apart(with_ties(rng, one_bin(rng, 594)), 40), "passes-refill", {"lds", "weight", "index"}
+    raise KeyError(name)
+
+
+ORDER_IDS = ["registers-256", "ranked-257", "ranked-2048", "ranked-rounds-2049", "one-pass", "passes", "passes-refill"]

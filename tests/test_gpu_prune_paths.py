@@ -12,6 +12,10 @@ case. PruneModel's input is then bit-equal to the oracle's, so the comparison wi
 test_gpu_round2.test_far_from_the_origin_stage_by_stage holds it to in that situation: count and order exact, weights
 1e-12, means 1e-13, the covariances' upper triangle 1e-9 (+ 1e-16).
 
+The sort half (phase A, prune_order) goes the same way: prune_cases.order_case has the smallest map for each of its branches
+— register sort, ranked with and without reload rounds, the one-pass fallback, the passes with and without refill —, means
+far apart so that the output is the sorted cut itself; the branch is predicted from the weights in numpy and asserted.
+
 The pass-through reads every record from the prior bank: the emitted records and the patched births are the last test's,
 a PRM3D frame whose detection updates and births merge, against orc.prune(orc.correct(orc.predict())) at the stage
 tolerance 1e-7."""
@@ -74,7 +78,8 @@ def prune_through_the_device(nav_mod, case, launch, what):
         timed_stage_run(nav, np.zeros((0, 3)), launch, what)
         cw, cm, cc = nav.CorrectConditional(0)
         assert len(cw) == len(case.w), "%s: the correction step kept %d of %d components" % (what, len(cw), len(case.w))
-        a, b = np.argsort(cw, kind="stable"), np.argsort(case.w, kind="stable")
+        # (by weight, bit-equal weights by their means: the corrected list is in no particular order)
+        a, b = np.lexsort((cm[:, 2], cm[:, 1], cm[:, 0], cw)), np.lexsort((case.mean[:, 2], case.mean[:, 1], case.mean[:, 0], case.w))
         assert np.array_equal(cw[a], case.w[b]) and np.array_equal(cm[a], case.mean[b]) and \
             np.array_equal(cc[a][:, IU[0], IU[1]], case.cov[b][:, IU[0], IU[1]]), "%s: the correction step did not pass the map on unchanged" % what
         got = nav.PruneModel(0)
@@ -105,6 +110,29 @@ def test_merge_paths_against_the_oracle(nav_mod, monkeypatch, name, launch):
         what, int(np.flatnonzero(~np.isclose(got[0], want[0], rtol=1e-12, atol=0))[0]))
     assert np.allclose(got[1], want[1], rtol=1e-13, atol=0), "%s: means (largest relative difference %g)" % (what, relative(got[1], want[1]))
     assert np.allclose(got[2][:, IU[0], IU[1]], want[2][:, IU[0], IU[1]], rtol=1e-9, atol=1e-16), "%s: covariances" % what
+
+
+# ---- the sort half: every branch of phase A (prune_order), at the smallest size that reaches it ---------------------------------------
+@pytest.mark.parametrize("launch", list(LAUNCHES))
+@pytest.mark.parametrize("name", pc.ORDER_IDS)
+def test_order_branches_against_the_oracle(nav_mod, monkeypatch, name, launch):
+    """Means far apart, so nothing merges and PruneModel's output is the sorted cut itself: count and order exact against
+    orc.prune, the weights bit-equal. Which branch a case takes — and, on the sorting branches, that neighbours among the kept
+    rows are told apart by the 32 weight bits in LDS, by the full weight and by the canonical index — is predicted from its
+    weights in numpy (prune_cases.order_branch, run_deciders) and asserted; the device is not asked."""
+    what = "%s through %s" % (name, launch)
+    case, branch, deciders = pc.order_case(name)
+    took = pc.order_branch(case.w, case.max_quantity, case.min_weight)
+    print("%s: %d weights, MaxQuantity %d: branch %s (sort width %d), run deciders %s" % (
+        what, len(case.w), case.max_quantity, took[0], took[2], sorted(pc.run_deciders(case.w, case.max_quantity, case.min_weight))))
+    assert took[0] == branch and deciders <= pc.run_deciders(case.w, case.max_quantity, case.min_weight)
+    select_launch(monkeypatch, launch)
+    p, got = prune_through_the_device(nav_mod, case, launch, what)
+    want = orc.prune(p, case.mix())
+    assert len(got[0]) == len(want[0]) == min(len(case.w), case.max_quantity)
+    assert np.array_equal(got[0], want[0]), "%s: weights / order, first difference at row %d" % (what, int(np.flatnonzero(got[0] != want[0])[0]))
+    assert np.allclose(got[1], want[1], rtol=1e-13, atol=0), "%s: means / order, first difference at row %d" % (
+        what, int(np.flatnonzero(~np.isclose(got[1], want[1], rtol=1e-13, atol=0).all(axis=1))[0]))
 
 
 # ---- rows that do not come from the prior bank: detection updates (emit_rec) and births (patched) ---------------------------------

@@ -28,6 +28,18 @@ def test_oracle_prune_equals_its_second_reading(name):
     assert np.array_equal(oc, rc), "covariances: first difference at row %d" % int(np.flatnonzero((oc != rc).any(axis=(1, 2)))[0])
 
 
+@pytest.mark.parametrize("name", pc.ORDER_IDS)
+def test_order_cases_reach_their_branch_of_phase_a(name):
+    """the maps that take the sort half of prune_merge_body down each of its branches (tests/test_gpu_prune_paths.py runs them on
+    the device): the branch is predicted from the weights alone, and nothing in such a map merges"""
+    case, branch, deciders = pc.order_case(name)
+    assert pc.order_branch(case.w, case.max_quantity, case.min_weight)[0] == branch
+    assert deciders <= pc.run_deciders(case.w, case.max_quantity, case.min_weight)
+    ow, om, oc = orc.prune(params_for(case), case.mix())
+    order = np.argsort(-case.w, kind="stable")[:min(case.max_quantity, len(case.w))]
+    assert np.array_equal(ow, case.w[order]) and np.allclose(om, case.mean[order], rtol=1e-15, atol=0)   # (Merge of one row: w m / w)
+
+
 def test_second_reading_on_a_hand_made_map():
     """three rows on a line, by hand: the heaviest takes the middle one; the lightest is outside the heaviest's distance and
     inside the middle row's (a covariance of 1), which is absorbed and so never asks: two rows out, the merged one with the
