@@ -51,6 +51,9 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_quasi_ascent(HandleRef nav, IntPtr initial6, int nestimates, IntPtr linearpoint7, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, int maxiterations, int rounditerations, IntPtr poses6, IntPtr values, IntPtr iterations, IntPtr hessians36);
 	[DllImport(Lib)] public extern static int    phd_set_depth_map(HandleRef nav, IntPtr depth, int width, int height);
 	[DllImport(Lib)] public extern static int    phd_slam_update(HandleRef nav, IntPtr z3, int nmeasurements, [MarshalAs(UnmanagedType.U1)] bool onlymapping, double uresample);
+	[DllImport(Lib)] public extern static int    phd_set_measurements(HandleRef nav, IntPtr z3, int nmeasurements);
+	[DllImport(Lib)] public extern static int    phd_step_hold_async(HandleRef nav, int held);
+	[DllImport(Lib)] public extern static int    phd_sync(HandleRef nav);
 	[DllImport(Lib)] public extern static IntPtr phd_weights(HandleRef nav, out int length);
 	[DllImport(Lib)] public extern static int    phd_best_particle(HandleRef nav);
 	[DllImport(Lib)] public extern static IntPtr phd_poses(HandleRef nav, out int length);
@@ -404,6 +407,63 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 		double[][] poses = new double[n][];
 		for (int i = 0; i < n; i++) { poses[i] = new double[6]; Array.Copy(result, 6 * i, poses[i], 0, 6); }
 		return poses;
+	}
+
+	Map MapOfParticle(int particle)
+	{
+		int n; IntPtr w, m, c;
+		Check(PhdHipLib.phd_map(nav, particle, out n, out w, out m, out c));
+		double[] ws = new double[n], ms = new double[3 * n], cs = new double[9 * n];
+		if (n > 0) { Marshal.Copy(w, ws, 0, n); Marshal.Copy(m, ms, 0, 3 * n); Marshal.Copy(c, cs, 0, 9 * n); }
+		Map map = new Map(3);
+		for (int i = 0; i < n; i++) {
+			double[][] cov = { new double[] {cs[9*i], cs[9*i+1], cs[9*i+2]}, new double[] {cs[9*i+3], cs[9*i+4], cs[9*i+5]}, new double[] {cs[9*i+6], cs[9*i+7], cs[9*i+8]} };
+			map.Add(new Gaussian(new double[] {ms[3*i], ms[3*i+1], ms[3*i+2]}, cov, ws[i]));
+		}
+		return map;
+	}
+
+	/// <summary>The maps LoopyPHDNavigator.FilterMissing (LoopyPHDNavigator.cs:729-762) gives for every frame below `to` left out
+	/// in turn — the loop of UpdateMessagesFromMap (:511-552) — and Filter's map over those frames (`full`), from one pass over the
+	/// frames: the leave-one-out filters are the particles of this handle stepped together, the particle that leaves frame k out
+	/// held through step k (phd_step_hold_async); one more particle is never held. This navigator is reset (mapping only, empty
+	/// maps); it must have been made for at least to + 1 particles (the Python and C++ mirrors run longer trajectories as several
+	/// passes). Nothing waits for the device until the one phd_sync at the end.</summary>
+	public Map[] DeviceLeaveOneOutMaps(List<Tuple<double, Pose3D>> trajectory, List<Tuple<double, List<PixelRangeMeasurement>>> factors, int to, out Map full)
+	{
+		to = Math.Max(0, Math.Min(trajectory.Count, to));
+		int count = to + 1;
+		double[] pose0 = (trajectory.Count > 0) ? trajectory[0].Item2.State : new double[] {0, 0, 0, 1, 0, 0, 0};
+		double[] none = new double[1];
+		fixed (double* pp = pose0) fixed (double* pn = none) {
+			Check(PhdHipLib.phd_reset(nav, count, (IntPtr) pp, (IntPtr) pn, (IntPtr) pn, (IntPtr) pn, 0));
+		}
+		double[] poses = new double[7 * count];
+		for (int k = 0; k < to; k++) {
+			for (int i = 0; i < count; i++) { trajectory[k].Item2.State.CopyTo(poses, 7 * i); }
+			List<PixelRangeMeasurement> measurements = factors[k].Item2;
+			double[] z = new double[Math.Max(1, 3 * measurements.Count)];
+			for (int i = 0; i < measurements.Count; i++) { measurements[i].ToLinear().CopyTo(z, 3 * i); }
+			fixed (double* pp = poses) fixed (double* pz = z) {
+				Check(PhdHipLib.phd_set_poses(nav, (IntPtr) pp, count));
+				Check(PhdHipLib.phd_set_measurements(nav, (IntPtr) pz, measurements.Count));   // (an empty set is a step like any other)
+			}
+			Check(PhdHipLib.phd_step_hold_async(nav, k));
+		}
+		Check(PhdHipLib.phd_sync(nav));
+		Map[] maps = new Map[to];
+		for (int k = 0; k < to; k++) { maps[k] = MapOfParticle(k); }
+		full = MapOfParticle(to);
+		// the managed mirror of the particle set follows the handle (as reset does)
+		VehicleParticles = new TrackVehicle<MeasurerT, Pose3D, PixelRangeMeasurement>[count];
+		for (int i = 0; i < count; i++) {
+			VehicleParticles[i] = RefVehicle.TrackClone(Config.MotionCovarianceMultiplier, Config.MeasurementCovarianceMultiplier,
+			                                            Config.NavigatorPD, Config.NavigatorClutterDensity, true);
+		}
+		VehicleWeights = new double[count];
+		for (int i = 0; i < count; i++) { VehicleWeights[i] = 1.0 / count; }
+		BestParticle = 0;
+		return maps;
 	}
 
 	/// <summary>≙ PHDNavigator.SlamUpdate (PHDNavigator.cs:323-362).</summary>

@@ -211,6 +211,24 @@ int phd_set_depth_map(phd_navigator* nav, const float* depth, int width, int hei
 int phd_test_detection_probability(phd_navigator* nav, const double* z3, int n, double* out);
 int phd_step_async(phd_navigator* nav, uint8_t onlymapping, double u_resample);
 int phd_sync(phd_navigator* nav);
+/* One mapping-only step that one particle sits out: in every respect phd_step_async(nav, 1, u) — the uniform is not used in
+ * mapping mode — except that particle slot `held` has, behind the step, exactly the mixture it had in front of it, bit for
+ * bit (component count, weights, means, covariances); its pose and weight are not touched. held == -1 holds nobody: the plain
+ * mapping step. What it is for: the T leave-one-out filters of the smoother (LoopyPHDNavigator.FilterMissing,
+ * LoopyPHDNavigator.cs:729-762, one per frame of UpdateMessagesFromMap :511-552) see the same poses and measurement sets and
+ * differ in the one frame each skips, so they are T particles of one handle stepped together, particle k held at frame k
+ * (LeaveOneOutMaps of the host mirrors; INTEGRATION.md, "Leave-one-out maps").
+ * The hold is a copy of the slot's records out of the current state in front of the step and back behind it, by two small
+ * kernels that look the current state up on the device (no step kernel knows of it): asynchronous, nothing waits for the
+ * host, correct right behind phd_step_async (also one that resampled), phd_set_poses, phd_set_measurements and another
+ * phd_step_hold_async. With 1024 particles or more a held step takes the fork / join order of the two streams (as behind any
+ * other call on the handle); held == -1 does not. A step that drops itself (a raised flag, found at phd_sync) leaves the old
+ * state, the held slot's included. The logs behave as behind phd_step_async. The side buffer (max_components records) is
+ * made at the first call with held >= 0.
+ * PHD_ERR_BAD_ARGUMENT, with nothing enqueued: a NULL handle, a handle without particles, `held` outside [-1, particles),
+ * frozen mode (phd_set_frozen), a multi-device handle, a handle that has run sharded steps.
+ * Hosts detect the call by symbol: the API version does not change.                                                        */
+int phd_step_hold_async(phd_navigator* nav, int held);
 /* Workspace of the set log-likelihood for data-association clusters of 65 .. 256 rows (MurtyPairing, GraphCombinatorics.cs:
  * 241-272, has no size limit; clusters of up to 64 rows work in a per-particle block and never fail): one slab per handle,
  * 128 MiB by default, about 0.4 MB per cluster of 128 rows and 1.3 MB per cluster of 256 in one step. When a step runs out

@@ -10,6 +10,7 @@
 #include "phd_maperror.h"
 #include "phd_poseerror.h"
 #include "phd_ascent.h"
+#include "phd_hold.h"
 #include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
 
 #include <algorithm>
@@ -135,6 +136,7 @@ struct phd_navigator {
 	DevBuf<double> d_outw;        // [Pcap][cap] the pruned weights as a plane (StepBufs::outw)
 	DevBuf<double> d_wcopy; DevBuf<int> d_cover;   // k_prune_merge -> k_alpha_density (see StepBufs)
 	DevBuf<double> d_motion;      // odometry[6] + noise[P][6] of phd_update_motion
+	DevBuf<double> d_hold; DevBuf<int> d_hold_count;   // phd_step_hold_async: the held slot's records [cap][10] and their count (phd_hold.h), made on first use
 	DevBuf<double> d_quasi;       // phd_quasi_set_loglik: poses[Pcap][7], landmarks[Jcap][3], z[256][3], out[Pcap]
 	PinBuf<int>    h_status;      // pinned mirror of [d_sel (two parities) | d_info | d_flags], one block on the device
 	PinBuf<double> h_quasi;       // ... its pinned mirror on the host (+ one word for the flags): one stream wait per call, no pageable copies
@@ -3099,6 +3101,46 @@ int phd_set_stream(phd_navigator* nav, void* stream, uint8_t lend)
 	enter(nav);
 	HC(hipStreamSynchronize(nav->stream));
 	nav->stream = lend ? (hipStream_t) stream : nav->own_stream;   // a NULL lent stream is the legacy default stream
+	return PHD_OK;
+}
+
+// (Last in the file: the two kernels are instantiated here, behind every other kernel of the code object, and move none of them.)
+// A mapping-only step that particle slot `held` sits out (phd_hold.h): its mixture is copied out of the current state in front of
+// the step and back into the current state behind it. Nothing of the step itself knows. Both copies run on `stream`; with two
+// sub-range streams the held step takes the fork / join order on both sides (pipe_ok = false: the stream the step forks from is
+// behind everything of the step before — its end left both streams ordered behind k_normalise_resample —, and the step's end
+// leaves `stream` behind everything of this one), and so does the step behind it. held == -1 is phd_step_async as it stands.
+int phd_step_hold_async(phd_navigator* nav, int held)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	MULTI_UNSUPPORTED(nav, "phd_step_hold_async");
+	if (nav->P < 1) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_hold_async: no particles (call phd_reset first)");
+	if (held < -1 || held >= nav->P) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_hold_async: `held` is a particle slot of the current state, or -1");
+	if (nav->frozen) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_hold_async: frozen mode (the state does not advance: nothing to hold)");
+	if (nav->sharded_used) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_step_hold_async: not available on a handle that has run sharded steps");
+	if (held < 0) return phd_step_async(nav, 1, 0.0);
+	if (!nav->d_hold) {
+		hipSetDevice(nav->device);
+		DevBuf<double> rec; DevBuf<int> cnt;
+		hipError_t e = rec.alloc((size_t) nav->cap * MIX_REC);
+		if (e == hipSuccess) e = cnt.alloc(1);
+		if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_step_hold_async: allocation: ") + hipGetErrorString(e));
+		nav->d_hold = std::move(rec); nav->d_hold_count = std::move(cnt);
+	}
+	enter(nav);
+	{
+		StepBufs b = make_bufs(nav);   // the roles in front of the step
+		hipLaunchKernelGGL((k_hold_save<int>), dim3(1), dim3(256), 0, nav->stream, b, held, nav->Pcap, (double*) nav->d_hold, (int*) nav->d_hold_count);
+		HC(hipGetLastError());
+	}
+	int rc = phd_step_async(nav, 1, 0.0);
+	if (rc) return rc;
+	{
+		StepBufs b = make_bufs(nav);   // ... and behind it (the parity has advanced)
+		hipLaunchKernelGGL((k_hold_restore<int>), dim3(1), dim3(256), 0, nav->stream, b, held, nav->Pcap, (const double*) nav->d_hold, (const int*) nav->d_hold_count);
+		HC(hipGetLastError());
+	}
+	nav->pipe_ok = false;   // the restore is on `stream` alone: the next step forks behind it
 	return PHD_OK;
 }
 

@@ -1,6 +1,7 @@
 // Loopy.hpp — C++ host mirror of the pose searches of the reference's smoother over libphdhip.so:
 //
 //   LoopyPHDNavigator.Filter / FilterMissing          SLAM/Navigators/LoopyPHDNavigator.cs:713-762
+//   ... every leave-one-out map in one pass            :511-552   (LeaveOneOutMaps: the loop around FilterMissing as held steps)
 //   LoopyPHDNavigator.LogLikeGradient                  :876-909   (12 evaluations, one device batch)
 //   LoopyPHDNavigator.LogLikeGradientAscent            :916-965   (any number of initial estimates side by side; the 16
 //                                                                  step sizes of a line search are one device batch)
@@ -93,6 +94,58 @@ inline Map Filter(PHDNavigator& filter, const std::vector<std::pair<double, Pose
                   const std::vector<std::pair<double, std::vector<PixelRangeMeasurement>>>& factors)
 {
 	return FilterMissing(filter, trajectory, factors, (int) trajectory.size(), (int) trajectory.size());
+}
+
+// The maps FilterMissing gives for each of `indices`, and Filter's over the frames < to (`full`), from ONE pass over the frames
+// (≙ the loop of UpdateMessagesFromMap, :511-552, around FilterMissing): the leave-one-out filters are the particles of one
+// handle stepped together, the particle that leaves frame k out held through step k (PHDNavigator::StepHold); one more particle
+// is never held. Every frame is posted without waiting, one Sync ends the pass. An index < 0 or >= to leaves nothing out
+// (:733-734), duplicates are allowed; more distinct indices than maxparticles - 1 (the handle's max_particles) run as several
+// passes, `full` is the first pass's. monorfs_amd/loopy.py has the Python twin.
+inline std::vector<Map> LeaveOneOutMaps(PHDNavigator& filter, const std::vector<std::pair<double, Pose3D>>& trajectory,
+                                        const std::vector<std::pair<double, std::vector<PixelRangeMeasurement>>>& factors,
+                                        const std::vector<int>& indices, int to, int maxparticles, Map* full = nullptr)
+{
+	to = std::max(0, std::min((int) trajectory.size(), to));
+	std::vector<int> distinct;
+	for (int i : indices) if (i >= 0 && i < to) distinct.push_back(i);
+	std::sort(distinct.begin(), distinct.end());
+	distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+	const int room = maxparticles - 1;
+	if (!distinct.empty() && room < 1) throw std::invalid_argument("LeaveOneOutMaps: a handle of at least two particles");
+	std::vector<Map> result(to);
+	Map fullmap;
+	bool havefull = false;
+	filter.OnlyMapping = true;
+	for (size_t s = 0; s < std::max<size_t>(distinct.size(), 1); s += (size_t) std::max(room, 1)) {
+		const int n = (int) std::min<size_t>((size_t) std::max(room, 0), distinct.size() - std::min(s, distinct.size()));
+		std::vector<int> slot(to, -1);
+		for (int j = 0; j < n; j++) slot[distinct[s + j]] = j;
+		const int count = n + 1;                   // the last particle is never held: the full map
+		filter.reset(trajectory.empty() ? Pose3D{0, 0, 0, 1, 0, 0, 0} : trajectory[0].second, Map(), count);
+		for (int k = 0; k < to; k++) {
+			filter.Update(std::vector<Pose3D>(count, trajectory[k].second));
+			filter.SetMeasurements(factors[k].second);
+			filter.StepHold(slot[k]);
+		}
+		filter.Sync();
+		for (int j = 0; j < n; j++) result[distinct[s + j]] = filter.MapModels(j);
+		if (!havefull) { fullmap = filter.MapModels(count - 1); havefull = true; }
+	}
+	std::vector<Map> maps;
+	for (int i : indices) maps.push_back((i >= 0 && i < to) ? result[i] : fullmap);
+	if (full) *full = fullmap;
+	return maps;
+}
+
+// ... for every frame < to
+inline std::vector<Map> LeaveOneOutMaps(PHDNavigator& filter, const std::vector<std::pair<double, Pose3D>>& trajectory,
+                                        const std::vector<std::pair<double, std::vector<PixelRangeMeasurement>>>& factors, int maxparticles, Map* full = nullptr)
+{
+	const int to = (int) trajectory.size();
+	std::vector<int> indices(to);
+	for (int i = 0; i < to; i++) indices[i] = i;
+	return LeaveOneOutMaps(filter, trajectory, factors, indices, to, maxparticles, full);
 }
 
 // ≙ LoopyPHDNavigator.LogLikeGradient (:876-909): central differences, eps = 1e-5

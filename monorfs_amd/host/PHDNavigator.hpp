@@ -283,6 +283,16 @@ public:
 		if (maphistory_) appendMapHistory(time);
 	}
 
+	// The step in its asynchronous parts (phd_set_measurements / phd_sync), and one mapping-only step that particle slot `held`
+	// sits out: behind it the slot has the mixture it had in front of it, bit for bit; -1 holds nobody (phd_step_hold_async).
+	// StepHold posts the step and returns; what a posted step finds surfaces at Sync.
+	void SetMeasurements(const std::vector<PixelRangeMeasurement>& measurements)
+	{
+		check(phd_set_measurements(nav_, measurements.empty() ? nullptr : measurements[0].data(), (int) measurements.size()));
+	}
+	void StepHold(int held) { check(phd_step_hold_async(nav_, held)); }
+	void Sync() { check(phd_sync(nav_)); }
+
 	std::vector<double> VehicleWeights()   // :128
 	{
 		int n = 0;

@@ -1,6 +1,7 @@
 """Host mirror of the pose searches of the reference's smoother: the static functions of
 LoopyPHDNavigator that evaluate QuasiSetLogLikelihood and its gradient for candidate poses against one map estimate
-and one measurement set (LoopyPHDNavigator.cs:718-1021), and Filter / FilterMissing (:713-762).
+and one measurement set (LoopyPHDNavigator.cs:718-1021), Filter / FilterMissing (:713-762), and LeaveOneOutMaps: the
+FilterMissing of every frame of UpdateMessagesFromMap (:511-552) from one pass of held steps.
 
 Every evaluation goes to the device through PHDNavigator.QuasiSetLogLikelihood / QuasiSetLogLikelihoodGradient
 (phd_quasi_set_loglik, phd_quasi_set_loglik_grad) as a BATCH: the 16 step sizes of a line search at once, all the
@@ -316,3 +317,56 @@ def FilterMissing(nav, trajectory, factors, index, to):
 def Filter(nav, trajectory, factors):
     """≙ LoopyPHDNavigator.Filter (:718-721)"""
     return FilterMissing(nav, trajectory, factors, len(trajectory), len(trajectory))
+
+
+def LeaveOneOutMaps(nav, trajectory, factors, indices=None, to=None):
+    """The maps FilterMissing gives for each of `indices`, and Filter's over the frames < to, from ONE pass over the frames:
+    returns (maps, full) with maps[j] bit for bit FilterMissing(nav, trajectory, factors, indices[j], to) and `full` the map
+    with nothing left out (≙ the loop of LoopyPHDNavigator.UpdateMessagesFromMap, :511-552, around FilterMissing :729-762).
+
+    The leave-one-out filters see the same poses and measurement sets and differ in the one frame each skips, and the
+    particles of a mapping-only step are independent: they are the particles of one handle stepped together, the particle
+    that leaves frame k out held through step k (PHDNavigator.StepHold, phd_step_hold_async); one more particle is never
+    held. `nav` is reset (mapping only, empty maps). Every frame is posted without waiting — poses, measurements (an empty
+    set is a step like any other), the held step —, one sync ends the pass and one download reads the maps.
+
+    indices: default every frame < to; an index < 0 or >= to leaves nothing out (:733-734), duplicates are allowed. More
+    distinct indices than max_particles - 1 run as several passes; `full` is the first pass's."""
+    to = len(trajectory) if to is None else min(len(trajectory), to)
+    indices = list(range(to)) if indices is None else [int(i) for i in indices]
+    distinct = sorted({i for i in indices if 0 <= i < to})
+    room = nav.params.max_particles - 1
+    if distinct and room < 1:
+        raise ValueError("LeaveOneOutMaps: a handle of at least two particles (one per left-out frame and one for the full map)")
+    empty = (np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3, 3)))
+    pose0 = np.asarray(trajectory[0][1], float) if len(trajectory) else np.array([0, 0, 0, 1.0, 0, 0, 0])
+    nav.OnlyMapping = True
+    result, full = {}, None
+    for s in range(0, max(len(distinct), 1), max(room, 1)):
+        chunk = distinct[s:s + room]
+        slot = {index: j for j, index in enumerate(chunk)}
+        count = len(chunk) + 1                    # the last particle is never held: the full map
+        nav.reset(pose0, empty, count)
+        for k in range(to):
+            nav.set_poses(np.tile(np.asarray(trajectory[k][1], float).reshape(1, 7), (count, 1)))
+            nav.set_measurements(np.asarray(factors[k][1], float).reshape(-1, 3))
+            nav.StepHold(slot.get(k, -1))
+        nav.sync()
+        _, counts, _, _ = nav.download_state(0)
+        planes, counts, _, _ = nav.download_state(max(int(counts.max()), 1))
+        models = [_model_of(planes, counts, j) for j in range(count)]
+        result.update({index: models[j] for index, j in slot.items()})
+        if full is None:
+            full = models[count - 1]
+    return [result.get(i, full) if 0 <= i < to else full for i in indices], full
+
+
+def _model_of(planes, counts, particle):
+    """(w, mean, cov) of one particle of a downloaded state: the device's records (covariance: upper triangle) as phd_map
+    hands them out"""
+    n = int(counts[particle])
+    r = planes[:, particle, :n]
+    cov = np.empty((n, 3, 3))
+    for f, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        cov[:, a, b] = cov[:, b, a] = r[4 + f]
+    return r[0].copy(), np.ascontiguousarray(r[1:4].T), cov

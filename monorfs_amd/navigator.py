@@ -525,6 +525,11 @@ class PHDNavigator:
     def step_async(self, u_resample=0.5):
         self._check(self._lib.phd_step_async(self._h, int(self.OnlyMapping), float(u_resample)))
 
+    def StepHold(self, held):
+        """One mapping-only step that particle slot `held` sits out: behind it the slot has the mixture it had in front of it,
+        bit for bit; -1 holds nobody (phd_step_hold_async). Posts the step and returns: nothing waits for the device."""
+        self._check(self._lib.phd_step_hold_async(self._h, int(held)))
+
     def sync(self):
         self._check(self._lib.phd_sync(self._h))
 
