@@ -49,6 +49,8 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik_grad(HandleRef nav, IntPtr poses7, int nposes, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, IntPtr result, IntPtr gradients6);
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik(HandleRef nav, IntPtr poses7, int nposes, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, IntPtr result);
 	[DllImport(Lib)] public extern static int    phd_quasi_ascent(HandleRef nav, IntPtr initial6, int nestimates, IntPtr linearpoint7, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, int maxiterations, int rounditerations, IntPtr poses6, IntPtr values, IntPtr iterations, IntPtr hessians36);
+	[DllImport(Lib)] public extern static int    phd_quasi_ascent_multi(HandleRef nav, int nproblems, IntPtr landmarkoffsets, IntPtr landmarks3, IntPtr measurementoffsets, IntPtr z3, IntPtr linearpoints7, IntPtr initial6, IntPtr problem, int nestimates, int averagemode, int maxiterations, int rounditerations, IntPtr poses6, IntPtr values, IntPtr iterations, IntPtr hessians36);
+	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik_multi(HandleRef nav, int nproblems, IntPtr landmarkoffsets, IntPtr landmarks3, IntPtr measurementoffsets, IntPtr z3, IntPtr poses7, IntPtr problem, int nposes, int averagemode, IntPtr values, IntPtr gradients6);
 	[DllImport(Lib)] public extern static int    phd_set_depth_map(HandleRef nav, IntPtr depth, int width, int height);
 	[DllImport(Lib)] public extern static int    phd_slam_update(HandleRef nav, IntPtr z3, int nmeasurements, [MarshalAs(UnmanagedType.U1)] bool onlymapping, double uresample);
 	[DllImport(Lib)] public extern static int    phd_set_measurements(HandleRef nav, IntPtr z3, int nmeasurements);
@@ -403,6 +405,42 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 				                                        averagemode, maxiterations, 0, (IntPtr) (pr + 6 * s), (IntPtr) (pv + s), (IntPtr) (pi + s), IntPtr.Zero);
 				if (status == StatusCapacity) { capped = true; } else { Check(status); }
 			}
+		}
+		double[][] poses = new double[n][];
+		for (int i = 0; i < n; i++) { poses[i] = new double[6]; Array.Copy(result, 6 * i, poses[i], 0, 6); }
+		return poses;
+	}
+
+	/// <summary>DeviceLogLikeGradientAscent for the estimates of many frames in the same launches (phd_quasi_ascent_multi): the
+	/// GuidedFitMixture of every frame of UpdateMessagesFromMap (LoopyPHDNavigator.cs:525-551). Frame q has the map estimate
+	/// maps[q], the measurements measurements[q] and the linearisation pose linearpoints[q]; estimate a starts at initial[a] and
+	/// belongs to frame problem[a]. Every estimate comes back as from DeviceLogLikeGradientAscent with its frame alone. One call
+	/// takes frames of one measurement-block class (up to 64, 65 to 128, 129 to 256 measurements; none fits any) and at most the
+	/// handle's max_particles / 16 estimates: a caller with more, or with mixed classes, makes several calls.</summary>
+	public double[][] DeviceLogLikeGradientAscentMulti(double[][] initial, int[] problem, List<List<PixelRangeMeasurement>> measurements, List<IMap> maps,
+	                                                   Pose3D[] linearpoints, out double[] loglike, out bool capped, int averagemode = 0, int maxiterations = 1000)
+	{
+		const int StatusCapacity = 2;                                     // PHD_ERR_CAPACITY
+		int n = initial.Length, np = maps.Count;
+		int[] lmoff = new int[np + 1], zoff = new int[np + 1];
+		for (int q = 0; q < np; q++) { lmoff[q + 1] = lmoff[q] + maps[q].Count; zoff[q + 1] = zoff[q] + measurements[q].Count; }
+		double[] z = new double[3 * zoff[np] + 3], lm = new double[3 * lmoff[np] + 3], p6 = new double[6 * n], lin = new double[7 * np];
+		for (int q = 0; q < np; q++) {
+			for (int i = 0; i < measurements[q].Count; i++) { measurements[q][i].ToLinear().CopyTo(z, 3 * (zoff[q] + i)); }
+			int j = lmoff[q];
+			foreach (Gaussian landmark in maps[q]) { landmark.Mean.CopyTo(lm, 3 * j++); }
+			linearpoints[q].State.CopyTo(lin, 7 * q);
+		}
+		for (int i = 0; i < n; i++) { initial[i].CopyTo(p6, 6 * i); }
+		double[] result = new double[6 * n];
+		int[] iterations = new int[n];
+		loglike = new double[n];
+		capped = false;
+		fixed (double* pz = z) fixed (double* pl = lm) fixed (double* pp = p6) fixed (double* plin = lin) fixed (double* pr = result) fixed (double* pv = loglike)
+		fixed (int* pi = iterations) fixed (int* plo = lmoff) fixed (int* pzo = zoff) fixed (int* pq = problem) {
+			int status = PhdHipLib.phd_quasi_ascent_multi(nav, np, (IntPtr) plo, (IntPtr) pl, (IntPtr) pzo, (IntPtr) pz, (IntPtr) plin, (IntPtr) pp, (IntPtr) pq, n,
+			                                              averagemode, maxiterations, 0, (IntPtr) pr, (IntPtr) pv, (IntPtr) pi, IntPtr.Zero);
+			if (status == StatusCapacity) { capped = true; } else { Check(status); }
 		}
 		double[][] poses = new double[n][];
 		for (int i = 0; i < n; i++) { poses[i] = new double[6]; Array.Copy(result, 6 * i, poses[i], 0, 6); }

@@ -574,6 +574,40 @@ int phd_quasi_ascent(phd_navigator* nav, const double* initial6, int nestimates,
                      double* poses6, double* values, int32_t* iterations,
                      double* hessians36 /* [nestimates][6][6] row-major, or NULL */);
 
+/* Pose searches of many frames in one call (monorfs_amd/csrc/phd_ascent_multi.h): the GuidedFitMixture of every frame of
+ * LoopyPHDNavigator.UpdateMessagesFromMap (:525-551) shares the launches of ONE chain. A PROBLEM is what differs between
+ * frames: a landmark set, a measurement set, a linearisation pose. Problem q has the landmarks landmarks3[landmark_offsets[q]
+ * .. landmark_offsets[q + 1]), the measurements z3[measurement_offsets[q] .. measurement_offsets[q + 1]) (both offset arrays
+ * [nproblems + 1], starting at 0, never decreasing) and linearpoints7[q]. Estimate e starts at initial6[e] and belongs to
+ * problem[e]; the estimates of a problem may sit anywhere, a problem may have none.
+ * For every estimate the outputs are bit for bit what phd_quasi_ascent returns for it when called with its problem alone at
+ * the same average_mode, max_iterations and round_iterations.
+ * Limits: PHD_ASCENT_LINE * nestimates <= max_particles; per problem landmarks <= min(1024, max_quantity rounded up to 64)
+ * and measurements <= min(max_measurements, 256); the measurement counts of ONE call lie in one block class — all in 0..64,
+ * all in 65..128 or all in 129..256, 0 fits any — (the wrappers split a mixed set). Everything is checked before anything
+ * is enqueued: a NULL handle or array, nproblems < 1, bad offsets, a problem index outside [0, nproblems), a limit, mixed
+ * classes, average_mode not 0 / 1, max_iterations < 1, round_iterations < 0 or non-finite input is PHD_ERR_BAD_ARGUMENT
+ * with the outputs untouched. PHD_ERR_ASSOCIATION and PHD_ERR_CAPACITY are call-wide, as for phd_quasi_ascent.
+ * Synchronous; a buffer of its own per handle (it grows to the largest call): the particle state, the logs, the step's and
+ * the single calls' flag words and slab counters are not touched; a multi-device handle uses its first shard.           */
+int phd_quasi_ascent_multi(phd_navigator* nav, int nproblems,
+                           const int32_t* landmark_offsets, const double* landmarks3,
+                           const int32_t* measurement_offsets, const double* z3,
+                           const double* linearpoints7 /* [nproblems][7] */,
+                           const double* initial6, const int32_t* problem, int nestimates,
+                           int average_mode, int max_iterations, int round_iterations,
+                           double* poses6, double* values, int32_t* iterations,
+                           double* hessians36 /* [nestimates][6][6] row-major, or NULL */);
+
+/* phd_quasi_set_loglik (gradients6 NULL: the value kernel, average_mode is not read beyond its range check) or
+ * phd_quasi_set_loglik_grad for poses of many problems in one launch: pose i is evaluated against problem[i], bit for bit
+ * as the single call with that problem alone. nposes <= max_particles; problems, limits and refusals as above.          */
+int phd_quasi_set_loglik_multi(phd_navigator* nav, int nproblems,
+                               const int32_t* landmark_offsets, const double* landmarks3,
+                               const int32_t* measurement_offsets, const double* z3,
+                               const double* poses7, const int32_t* problem, int nposes,
+                               int average_mode, double* out, double* gradients6 /* or NULL */);
+
 /* Test surface for the control kernels of phd_quasi_ascent: k_ascent_candidates, then k_ascent_select on the caller's
  * values16[nestimates][16], no evaluation in between, every estimate active. Returns cand6[n][16][6], cand7[n][16][7], the
  * index of the candidate the line search ended on, the new pose6 / loglike, nextpose7 and the active word.              */

@@ -30,7 +30,8 @@
 
 struct AscentBufs {
 	int n;                        // estimates of this call
-	const double* lin;            // [7] the linearisation pose
+	const double* lin;            // [7] the linearisation pose ([problems][7] with `problem`)
+	const int* problem;           // [n] the problem of estimate e (phd_ascent_multi.h); NULL: every estimate belongs to problem 0
 	int* flags;                   // the batch's flag word
 	unsigned long long* slab;     // ... and its slab counter (StepBufs::bigws_used of the evaluation launches)
 	int* nactive;                 // estimates still active behind the last k_ascent_select
@@ -51,6 +52,9 @@ struct AscentBufs {
 	double* hgrad;                // [n][12][6]
 	double* hval;                 // [n][12]
 };
+
+// the linearisation pose of estimate e
+__device__ __forceinline__ const double* ascent_lin(const AscentBufs& s, int e) { return s.lin + 7 * (size_t) (s.problem ? s.problem[e] : 0); }
 
 // Pose3D.Add (Pose3D.cs:282-291) as navigator.py::pose3d_add states it: x + q dx q*, q Exp(dr / 2) normalised
 __device__ __forceinline__ void ascent_pose_add(const double* __restrict__ lin, const double d[6], double* __restrict__ out)
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(256) void k_ascent_begin(const AscentBufs s)
 	double d[6];
 #pragma unroll
 	for (int t = 0; t < 6; t++) d[t] = s.pose6[(size_t) i * 6 + t];
-	ascent_pose_add(s.lin, d, s.nextpose7 + (size_t) i * 7);
+	ascent_pose_add(ascent_lin(s, i), d, s.nextpose7 + (size_t) i * 7);
 	s.prev[i]       = -INFINITY;
 	s.iterations[i] = 0;
 	s.active[i]     = 1;
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void k_ascent_candidates(const AscentBufs s)
 		d[k] = s.pose6[(size_t) e * 6 + k] + m * g[k];
 		s.cand6[(size_t) t * 6 + k] = d[k];
 	}
-	ascent_pose_add(s.lin, d, s.cand7 + (size_t) t * 7);
+	ascent_pose_add(ascent_lin(s, e), d, s.cand7 + (size_t) t * 7);
 }
 
 // one thread per estimate: c = 0; do { v = values[c]; c++; } while (v < loglike && c < 16); (:943-951) and what follows it
@@ -181,7 +185,7 @@ __global__ __launch_bounds__(256) void k_ascent_hess_poses(const AscentBufs s)
 		d[k] = s.pose6[(size_t) e * 6 + k];
 		if (k == i) d[k] = d[k] + step;
 	}
-	ascent_pose_add(s.lin, d, s.hpose + (size_t) t * 7);
+	ascent_pose_add(ascent_lin(s, e), d, s.hpose + (size_t) t * 7);
 }
 
 // H[i][j] = (g(+i)[j] - g(-i)[j]) / (2 eps), raw: the NaN test, the eigenvalue clip and the pseudo-inverse are the host's

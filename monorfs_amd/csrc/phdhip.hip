@@ -10,6 +10,7 @@
 #include "phd_maperror.h"
 #include "phd_poseerror.h"
 #include "phd_ascent.h"
+#include "phd_ascent_multi.h"
 #include "phd_hold.h"
 #include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
 
@@ -27,6 +28,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <functional>
 #include <vector>
 
 #define DSPLIT_ROWS 1024     // particles the helpers' words are allocated for (k_particle_chain with helper workgroups)
@@ -142,6 +144,9 @@ struct phd_navigator {
 	PinBuf<double> h_quasi;       // ... its pinned mirror on the host (+ one word for the flags): one stream wait per call, no pageable copies
 	DevBuf<double> d_ascent;      // phd_quasi_ascent: the inputs, the per-estimate state and the results of one call (ascent_layout), made on first use
 	PinBuf<double> h_ascent;      // ... the pinned mirror of what is copied in and out, and the word the host reads between rounds
+	DevBuf<double> d_amulti;      // phd_quasi_ascent_multi / phd_quasi_set_loglik_multi: the same for a call over many problems (multi_layout); grows to the largest call
+	PinBuf<double> h_amulti;
+	size_t amulti_cap = 0;        // doubles either holds
 	DevBuf<double> d_gw; int gwcap = 0;              // gathered weights of all ranks (+ their status words behind them: flagslot)
 	DevBuf<double> d_stage;                          // device staging of phd_set_poses / phd_set_weights (stored into the IN bank by k_store_small)
 	// pinned host staging of the per-frame inputs (poses, weights, odometry + noise, measurements): the caller's buffers are
@@ -453,6 +458,8 @@ struct StepVariant {
 	void (*quasi_grad)(DevParams, StepBufs, int);
 	void (*ascent)(DevParams, StepBufs, int, const int*, int);        // the same two bodies for phd_quasi_ascent: workgroups of stopped estimates return
 	void (*ascent_grad)(DevParams, StepBufs, int, const int*, int);
+	void (*multi)(DevParams, StepBufs, int, QuasiProblems, const int*, int);   // ... with the landmark and measurement set of the estimate's problem bound in (phd_ascent_multi.h)
+	void (*multi_grad)(DevParams, StepBufs, int, QuasiProblems, const int*, int);
 	int  (*chain_pool)(int);
 	int zi() const { return zb >> 1; }   // index of ZB = 1, 2, 4 (phd_navigator::chain_ok)
 	int chain_lds(int cutcap) const { return chain_pool(cutcap); }
@@ -464,7 +471,7 @@ template <int ZB, bool HALF, bool DEPTH>
 StepVariant make_variant()
 {
 	return {ZB, HALF, DEPTH, k_particle_chain<ZB, HALF, DEPTH>, k_sweep<ZB, HALF, DEPTH>, k_emit_prune<DEPTH>, k_emit_finish<DEPTH>, k_alpha_assoc<ZB, DEPTH>,
-	        k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, k_ascent_setll<ZB>, k_ascent_setll_grad<ZB>, chain_lds_bytes<ZB>};
+	        k_quasi_setll<ZB>, k_quasi_setll_grad<ZB>, k_ascent_setll<ZB>, k_ascent_setll_grad<ZB>, k_multi_setll<ZB>, k_multi_setll_grad<ZB>, chain_lds_bytes<ZB>};
 }
 
 const StepVariant step_variants[8] = {make_variant<1, false, false>(), make_variant<1, true, false>(), make_variant<2, false, false>(), make_variant<4, false, false>(),
@@ -999,6 +1006,8 @@ phd_navigator* phd_create(const phd_params* params, int device)
 				raise(v.quasi_grad, la);
 				raise(v.ascent, la);
 				raise(v.ascent_grad, la);
+				raise(v.multi, la);
+				raise(v.multi_grad, la);
 				lim.alpha[i] = la;
 			}
 			// the one-launch chain: its bodies share one pool, the largest of their layouts, which must fit a workgroup (160 KB)
@@ -1244,7 +1253,7 @@ AscentLayout ascent_layout(size_t n, size_t J, size_t M)
 AscentBufs ascent_bufs(double* d, const AscentLayout& l, int n)
 {
 	AscentBufs s;
-	s.n = n; s.lin = d + l.lin;
+	s.n = n; s.lin = d + l.lin; s.problem = nullptr;
 	s.flags = (int*) (d + l.head); s.slab = (unsigned long long*) (d + l.head + 1); s.nactive = (int*) (d + l.head + 2);
 	s.pose6 = d + l.pose6; s.loglike = d + l.loglike; s.iterations = (int*) (d + l.iters); s.hess = d + l.hess;
 	s.nextpose7 = d + l.next7; s.prev = d + l.prev; s.active = (int*) (d + l.active); s.chosen = (int*) (d + l.chosen);
@@ -1278,6 +1287,146 @@ int ascent_eval(phd_navigator* nav, const AscentBufs& s, const AscentLayout& l, 
 }
 
 inline int ascent_blocks(int threads) { return (threads + 255) / 256; }
+
+// The chain of one call, enqueued on the handle's stream: begin, the first gradient launch, the iterations in rounds with one
+// look at the active count between two rounds, the Hessian rows. `eval(poses7, nposes, setll, qgrad, active, group)` launches an
+// evaluation: phd_quasi_ascent's own (ascent_eval) or the one over many problems (multi_eval). `word`: pinned, for that look.
+using AscentEval = std::function<int(const double*, int, double*, double*, const int*, int)>;
+int ascent_chain(phd_navigator* nav, const AscentBufs& s, int max_iterations, int round_iterations, bool hessians, int* word, const AscentEval& eval)
+{
+	const int n = s.n;
+	hipStream_t st = nav->stream;
+	hipLaunchKernelGGL(k_ascent_begin, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
+	int rc = eval(s.nextpose7, n, s.gval, s.grad, nullptr, 1);
+	if (rc) return rc;
+	hipLaunchKernelGGL(k_ascent_start, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
+	const int round = round_iterations > 0 ? round_iterations : PHD_ASCENT_ROUND;
+	int done = 0;
+	while (done < max_iterations) {
+		const int upto = std::min(max_iterations, done + round);
+		for (; done < upto; done++) {
+			if (done > 0) {   // (iteration 0 keeps the first launch's gradient: the same pose through the same kernel)
+				rc = eval(s.nextpose7, n, s.gval, s.grad, s.active, 1);
+				if (rc) return rc;
+			}
+			hipLaunchKernelGGL(k_ascent_candidates, dim3(ascent_blocks(n * PHD_ASCENT_LINE)), dim3(256), 0, st, s);
+			rc = eval(s.cand7, n * PHD_ASCENT_LINE, s.values, nullptr, s.active, PHD_ASCENT_LINE);
+			if (rc) return rc;
+			hipLaunchKernelGGL(k_ascent_select, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
+		}
+		if (done >= max_iterations) break;   // (the count comes with the results)
+		HC(hipMemcpyAsync(word, s.nactive, 4, hipMemcpyDeviceToHost, st));
+		HC(hipStreamSynchronize(st));
+		if (*word == 0) break;
+	}
+	if (hessians) {
+		hipLaunchKernelGGL(k_ascent_hess_poses, dim3(ascent_blocks(n * 12)), dim3(256), 0, st, s);
+		rc = eval(s.hpose, n * 12, s.hval, s.hgrad, nullptr, 12);   // (12 poses per estimate: the group tells a launch over many problems whose pose it has)
+		if (rc) return rc;
+		hipLaunchKernelGGL(k_ascent_hess_rows, dim3(ascent_blocks(n * 36)), dim3(256), 0, st, s);
+	}
+	HC(hipGetLastError());
+	return PHD_OK;
+}
+
+// ---- many problems in one call (phd_ascent_multi.h). One buffer per handle, grown to the largest call, in doubles (the int
+// arrays two to a double):
+//   lm_off[np + 1] | z_off[np + 1] | problem[n] | landmarks[sum J][3] | z[sum M][3] | lin[np][7] | head[4] | pose6[n][6]   <- ONE copy in
+// and from `head` on what ascent_layout states: the copy out, then the state that never leaves the device. The batch calls put
+// poses7[n][7] where lin stands and out[n] | gradients[n][6] behind head. The flag word and the slab counter in `head` are this
+// buffer's own: the step and the single calls find theirs untouched.
+struct MultiLayout {
+	size_t lmoff, zoff, problem, lm, z, lin, head;
+	AscentLayout a;   // ascent_layout's offsets from `head` on, within this buffer
+};
+
+MultiLayout multi_layout(size_t np, size_t n, size_t sumJ, size_t sumM, size_t lin_doubles)
+{
+	MultiLayout l;
+	l.lmoff = 0; l.zoff = l.lmoff + (np + 2) / 2; l.problem = l.zoff + (np + 2) / 2; l.lm = l.problem + (n + 1) / 2;
+	l.z = l.lm + sumJ * 3; l.lin = l.z + sumM * 3; l.head = l.lin + lin_doubles;
+	l.a = ascent_layout(n, 0, 0);
+	const size_t shift = l.head - l.a.head;
+	for (size_t* f : {&l.a.head, &l.a.pose6, &l.a.loglike, &l.a.iters, &l.a.hess, &l.a.out_end, &l.a.next7, &l.a.prev, &l.a.active, &l.a.chosen, &l.a.grad,
+	                  &l.a.gval, &l.a.cand6, &l.a.cand7, &l.a.values, &l.a.hpose, &l.a.hgrad, &l.a.hval, &l.a.end}) *f += shift;
+	l.a.lin = l.lin; l.a.lm = l.lm; l.a.z = l.z;
+	return l;
+}
+
+// room for `doubles` and the word read between rounds behind them; a reallocation waits for what the stream still holds
+int multi_ensure(phd_navigator* nav, size_t doubles)
+{
+	if (nav->d_amulti && nav->h_amulti && doubles + 1 <= nav->amulti_cap) return PHD_OK;
+	HC(hipStreamSynchronize(nav->stream));
+	nav->amulti_cap = 0;
+	HC(nav->d_amulti.alloc(doubles + 1));
+	HC(nav->h_amulti.alloc(doubles + 1, hipHostMallocDefault));
+	nav->amulti_cap = doubles + 1;
+	return PHD_OK;
+}
+
+// The host's checks of a problem table, before anything is enqueued: the kernels index the pools with what passes here. zb: the
+// block class of the call (1, 2, 4), 1 where no problem has a measurement.
+int multi_validate(phd_navigator* nav, const char* who, int nproblems, const int32_t* lmoff, const double* landmarks3, const int32_t* zoff, const double* z3,
+                   const int32_t* problem, int n, int* zb)
+{
+	const std::string w(who);
+	if (nproblems < 1 || !lmoff || !zoff || !problem) return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": nproblems < 1 or a NULL array");
+	if (lmoff[0] != 0 || zoff[0] != 0) return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": an offsets array does not start at 0");
+	const int mmax = std::min(nav->prm.max_measurements, 256);
+	int cls = 0;
+	for (int q = 0; q < nproblems; q++) {
+		const long long J = (long long) lmoff[q + 1] - lmoff[q], M = (long long) zoff[q + 1] - zoff[q];
+		if (J < 0 || M < 0) return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": an offsets array decreases");
+		if (J > nav->Jcap || M > mmax) {
+			return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": a problem is out of range (landmarks <= min(1024, max_quantity rounded up to 64), measurements <= min(max_measurements, 256))");
+		}
+		if (M > 0) {
+			const int c = zb_of((int) M);
+			if (cls && c != cls) return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": the measurement counts of one call lie in one block class (0..64, 65..128 or 129..256)");
+			cls = c;
+		}
+	}
+	if ((lmoff[nproblems] && !landmarks3) || (zoff[nproblems] && !z3)) return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": a NULL pool");
+	for (int e = 0; e < n; e++) {
+		if (problem[e] < 0 || problem[e] >= nproblems) return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": a problem index outside [0, nproblems)");
+	}
+	if (!all_finite(landmarks3, (size_t) lmoff[nproblems] * 3) || !all_finite(z3, (size_t) zoff[nproblems] * 3)) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, w + ": non-finite input (NaN or infinity) is not accepted");
+	}
+	*zb = cls ? cls : 1;
+	return PHD_OK;
+}
+
+// the table and the pools into the pinned mirror; the device's view of them
+QuasiProblems multi_pack(double* h, double* d, const MultiLayout& l, int nproblems, const int32_t* lmoff, const double* landmarks3, const int32_t* zoff,
+                         const double* z3, const int32_t* problem, int n)
+{
+	std::memcpy(h + l.lmoff, lmoff, (size_t) (nproblems + 1) * 4);
+	std::memcpy(h + l.zoff, zoff, (size_t) (nproblems + 1) * 4);
+	std::memcpy(h + l.problem, problem, (size_t) n * 4);
+	if (lmoff[nproblems]) std::memcpy(h + l.lm, landmarks3, (size_t) lmoff[nproblems] * 3 * 8);
+	if (zoff[nproblems]) std::memcpy(h + l.z, z3, (size_t) zoff[nproblems] * 3 * 8);
+	QuasiProblems pr;
+	pr.problem = (const int*) (d + l.problem); pr.lm_off = (const int*) (d + l.lmoff); pr.z_off = (const int*) (d + l.zoff);
+	pr.lm = d + l.lm; pr.z = d + l.z; pr.lin = d + l.lin;
+	return pr;
+}
+
+// an evaluation launch over many problems: M, z, qlm and qJ of `b` are bound per workgroup by the kernel
+int multi_eval(phd_navigator* nav, const QuasiProblems& pr, int zb, int* flags, unsigned long long* slab, int average_mode, const double* poses7, int nposes,
+               double* setll, double* qgrad, const int* active, int group)
+{
+	StepBufs b = make_bufs(nav);
+	b.P = nposes; b.M = 0; b.z = pr.z;
+	b.qposes = poses7; b.qlm = pr.lm; b.qJ = 0;
+	b.setll = setll; b.qgrad = qgrad; b.qavg = average_mode;
+	b.flags = flags; b.bigws_used = slab;
+	const StepVariant& v = variant(zb * 64, false);
+	hipLaunchKernelGGL(qgrad ? v.multi_grad : v.multi, dim3(nposes), dim3(256), (size_t) v.assoc_lds(nav->cutcap), nav->stream, nav->dp, b, nav->cutcap, pr, active, group);
+	HC(hipGetLastError());
+	return PHD_OK;
+}
 
 }  // namespace
 
@@ -1314,37 +1463,12 @@ int phd_quasi_ascent(phd_navigator* nav, const double* initial6, int nestimates,
 	std::memcpy(h + l.pose6, initial6, (size_t) n * 6 * 8);
 	HC(hipMemcpyAsync(d, h, l.loglike * 8, hipMemcpyHostToDevice, nav->stream));
 	hipStream_t st = nav->stream;
-	hipLaunchKernelGGL(k_ascent_begin, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
-	rc = ascent_eval(nav, s, l, J, M, average_mode, s.nextpose7, n, s.gval, s.grad, nullptr, 1);
-	if (rc) return rc;
-	hipLaunchKernelGGL(k_ascent_start, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
-	const int round = round_iterations > 0 ? round_iterations : PHD_ASCENT_ROUND;
 	int* const word = (int*) (h + ascent_layout((size_t) (nav->Pcap / PHD_ASCENT_LINE), (size_t) nav->Jcap, 256).end);
-	int done = 0;
-	while (done < max_iterations) {
-		const int upto = std::min(max_iterations, done + round);
-		for (; done < upto; done++) {
-			if (done > 0) {   // (iteration 0 keeps the first launch's gradient: the same pose through the same kernel)
-				rc = ascent_eval(nav, s, l, J, M, average_mode, s.nextpose7, n, s.gval, s.grad, s.active, 1);
-				if (rc) return rc;
-			}
-			hipLaunchKernelGGL(k_ascent_candidates, dim3(ascent_blocks(n * PHD_ASCENT_LINE)), dim3(256), 0, st, s);
-			rc = ascent_eval(nav, s, l, J, M, average_mode, s.cand7, n * PHD_ASCENT_LINE, s.values, nullptr, s.active, PHD_ASCENT_LINE);
-			if (rc) return rc;
-			hipLaunchKernelGGL(k_ascent_select, dim3(ascent_blocks(n)), dim3(256), 0, st, s);
-		}
-		if (done >= max_iterations) break;   // (the count comes with the results)
-		HC(hipMemcpyAsync(word, s.nactive, 4, hipMemcpyDeviceToHost, st));
-		HC(hipStreamSynchronize(st));
-		if (*word == 0) break;
-	}
-	if (hessians36) {
-		hipLaunchKernelGGL(k_ascent_hess_poses, dim3(ascent_blocks(n * 12)), dim3(256), 0, st, s);
-		rc = ascent_eval(nav, s, l, J, M, average_mode, s.hpose, n * 12, s.hval, s.hgrad, nullptr, 1);
-		if (rc) return rc;
-		hipLaunchKernelGGL(k_ascent_hess_rows, dim3(ascent_blocks(n * 36)), dim3(256), 0, st, s);
-	}
-	HC(hipGetLastError());
+	rc = ascent_chain(nav, s, max_iterations, round_iterations, hessians36 != nullptr, word,
+	                  [&](const double* poses7, int nposes, double* setll, double* qgrad, const int* active, int group) {
+		return ascent_eval(nav, s, l, J, M, average_mode, poses7, nposes, setll, qgrad, active, group);
+	});
+	if (rc) return rc;
 	HC(hipMemcpyAsync(h + l.head, d + l.head, ((hessians36 ? l.out_end : l.hess) - l.head) * 8, hipMemcpyDeviceToHost, st));
 	HC(hipStreamSynchronize(st));
 	std::memcpy(poses6, h + l.pose6, (size_t) n * 6 * 8);
@@ -1359,6 +1483,108 @@ int phd_quasi_ascent(phd_navigator* nav, const double* initial6, int nestimates,
 	}
 	if (nactive > 0) {
 		return nav->fail(PHD_ERR_CAPACITY, "phd_quasi_ascent: estimates were still climbing after max_iterations iterations (their state at the bound is returned)");
+	}
+	return PHD_OK;
+}
+
+// phd_quasi_ascent for the estimates of many problems in the same launches: estimate e is searched against problem problem[e]
+int phd_quasi_ascent_multi(phd_navigator* nav, int nproblems, const int32_t* landmark_offsets, const double* landmarks3,
+                           const int32_t* measurement_offsets, const double* z3, const double* linearpoints7,
+                           const double* initial6, const int32_t* problem, int nestimates,
+                           int average_mode, int max_iterations, int round_iterations,
+                           double* poses6, double* values, int32_t* iterations, double* hessians36)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);   // as the single call
+	const char* who = "phd_quasi_ascent_multi";
+	const int n = nestimates;
+	if (n < 1 || (long long) n * PHD_ASCENT_LINE > nav->Pcap || !initial6 || !linearpoints7 || !poses6 || !values || !iterations) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_ascent_multi: 1 <= estimates, 16 x estimates <= max_particles, no NULL array");
+	}
+	if (average_mode < 0 || average_mode > 1 || max_iterations < 1 || round_iterations < 0) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_ascent_multi: average_mode is not 0 / 1, max_iterations < 1 or round_iterations < 0");
+	}
+	int zb = 1;
+	int rc = multi_validate(nav, who, nproblems, landmark_offsets, landmarks3, measurement_offsets, z3, problem, n, &zb);
+	if (rc) return rc;
+	FINITE_OR_FAIL(nav, initial6, (size_t) n * 6, "phd_quasi_ascent_multi");
+	FINITE_OR_FAIL(nav, linearpoints7, (size_t) nproblems * 7, "phd_quasi_ascent_multi");
+	enter(nav);
+	const MultiLayout l = multi_layout(nproblems, n, landmark_offsets[nproblems], measurement_offsets[nproblems], (size_t) nproblems * 7);
+	rc = multi_ensure(nav, l.a.end);
+	if (rc) return rc;
+	double* const d = nav->d_amulti;
+	double* const h = nav->h_amulti;
+	const QuasiProblems pr = multi_pack(h, d, l, nproblems, landmark_offsets, landmarks3, measurement_offsets, z3, problem, n);
+	AscentBufs s = ascent_bufs(d, l.a, n);
+	s.problem = pr.problem;
+	std::memcpy(h + l.lin, linearpoints7, (size_t) nproblems * 7 * 8);
+	std::memset(h + l.head, 0, 4 * 8);
+	std::memcpy(h + l.a.pose6, initial6, (size_t) n * 6 * 8);
+	hipStream_t st = nav->stream;
+	HC(hipMemcpyAsync(d, h, l.a.loglike * 8, hipMemcpyHostToDevice, st));
+	int* const word = (int*) (h + nav->amulti_cap - 1);
+	rc = ascent_chain(nav, s, max_iterations, round_iterations, hessians36 != nullptr, word,
+	                  [&](const double* poses7, int nposes, double* setll, double* qgrad, const int* active, int group) {
+		return multi_eval(nav, pr, zb, s.flags, s.slab, average_mode, poses7, nposes, setll, qgrad, active, group);
+	});
+	if (rc) return rc;
+	HC(hipMemcpyAsync(h + l.head, d + l.head, ((hessians36 ? l.a.out_end : l.a.hess) - l.head) * 8, hipMemcpyDeviceToHost, st));
+	HC(hipStreamSynchronize(st));
+	std::memcpy(poses6, h + l.a.pose6, (size_t) n * 6 * 8);
+	std::memcpy(values, h + l.a.loglike, (size_t) n * 8);
+	std::memcpy(iterations, h + l.a.iters, (size_t) n * 4);
+	if (hessians36) std::memcpy(hessians36, h + l.a.hess, (size_t) n * 36 * 8);
+	int flags = 0, nactive = 0;
+	std::memcpy(&flags, h + l.head, 4);
+	std::memcpy(&nactive, h + l.head + 2, 4);
+	if (flags & PHD_FLAG_BIG_CLUSTER) {
+		return nav->fail(PHD_ERR_ASSOCIATION, "phd_quasi_ascent_multi: an association cluster exceeds the on-device solver");
+	}
+	if (nactive > 0) {
+		return nav->fail(PHD_ERR_CAPACITY, "phd_quasi_ascent_multi: estimates were still climbing after max_iterations iterations (their state at the bound is returned)");
+	}
+	return PHD_OK;
+}
+
+// phd_quasi_set_loglik / phd_quasi_set_loglik_grad for poses of many problems in one launch: pose i is evaluated against problem[i]
+int phd_quasi_set_loglik_multi(phd_navigator* nav, int nproblems, const int32_t* landmark_offsets, const double* landmarks3,
+                               const int32_t* measurement_offsets, const double* z3, const double* poses7, const int32_t* problem, int nposes,
+                               int average_mode, double* out, double* gradients6)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);
+	const char* who = "phd_quasi_set_loglik_multi";
+	const int n = nposes;
+	if (n < 1 || n > nav->Pcap || !poses7 || !out || average_mode < 0 || average_mode > 1) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_set_loglik_multi: 1 <= poses <= max_particles, no NULL array, average_mode 0 / 1");
+	}
+	int zb = 1;
+	int rc = multi_validate(nav, who, nproblems, landmark_offsets, landmarks3, measurement_offsets, z3, problem, n, &zb);
+	if (rc) return rc;
+	FINITE_OR_FAIL(nav, poses7, (size_t) n * 7, "phd_quasi_set_loglik_multi");
+	enter(nav);
+	const MultiLayout l = multi_layout(nproblems, n, landmark_offsets[nproblems], measurement_offsets[nproblems], (size_t) n * 7);
+	const size_t oo = l.head + 4, og = oo + n, end = og + (gradients6 ? (size_t) n * 6 : 0);
+	rc = multi_ensure(nav, end);
+	if (rc) return rc;
+	double* const d = nav->d_amulti;
+	double* const h = nav->h_amulti;
+	const QuasiProblems pr = multi_pack(h, d, l, nproblems, landmark_offsets, landmarks3, measurement_offsets, z3, problem, n);
+	std::memcpy(h + l.lin, poses7, (size_t) n * 7 * 8);   // (the poses stand where an ascent has its linearisation poses)
+	std::memset(h + l.head, 0, 4 * 8);
+	hipStream_t st = nav->stream;
+	HC(hipMemcpyAsync(d, h, oo * 8, hipMemcpyHostToDevice, st));
+	rc = multi_eval(nav, pr, zb, (int*) (d + l.head), (unsigned long long*) (d + l.head + 1), gradients6 ? average_mode : 0, d + l.lin, n, d + oo, gradients6 ? d + og : nullptr, nullptr, 1);
+	if (rc) return rc;
+	HC(hipMemcpyAsync(h + l.head, d + l.head, (end - l.head) * 8, hipMemcpyDeviceToHost, st));
+	HC(hipStreamSynchronize(st));
+	std::memcpy(out, h + oo, (size_t) n * 8);
+	if (gradients6) std::memcpy(gradients6, h + og, (size_t) n * 6 * 8);
+	int flags = 0;
+	std::memcpy(&flags, h + l.head, 4);
+	if (flags & PHD_FLAG_BIG_CLUSTER) {
+		return nav->fail(PHD_ERR_ASSOCIATION, "phd_quasi_set_loglik_multi: an association cluster exceeds the on-device solver");
 	}
 	return PHD_OK;
 }

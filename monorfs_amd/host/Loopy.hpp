@@ -416,6 +416,54 @@ struct PoseComponent {   // a component of the fitted mixture over linear poses
 	Matrix6  covariance;
 };
 
+namespace detail {
+// the tail of GuidedFitMixture (:825-850): the maxima in order, one within Mahalanobis 0.1 of an earlier component dropped,
+// every component with the covariance fitted at pose0 (`localcov`, asked for on first need)
+template <class Cov>
+inline std::vector<PoseComponent> MixtureOf(const std::vector<Odometry>& poses, const std::vector<double>& values, Cov&& fitcovariance)
+{
+	std::vector<PoseComponent> components;
+	bool havecov = false;
+	Matrix6 localcov{};
+	auto pinvquad = [](const Matrix6& cov, const Odometry& d) {   // d' pinv(cov) d
+		Matrix6 V;
+		std::array<double, 6> vals;
+		detail::SymEig6(cov, vals, V);
+		double lmax = 0, q = 0;
+		for (double x : vals) lmax = std::max(lmax, std::fabs(x));
+		for (int e = 0; e < 6; e++) {
+			if (!(std::fabs(vals[e]) > 1e-15 * lmax)) continue;
+			double proj = 0;
+			for (int i = 0; i < 6; i++) proj += V[i * 6 + e] * d[i];
+			q += proj * proj / vals[e];
+		}
+		return q;
+	};
+	for (size_t a = 0; a < poses.size(); a++) {
+		bool counted = false;
+		for (const PoseComponent& c : components) {
+			Odometry d;
+			for (int t = 0; t < 6; t++) d[t] = c.mean[t] - poses[a][t];
+			if (std::sqrt(std::max(0.0, pinvquad(c.covariance, d))) < 0.1) { counted = true; break; }
+		}
+		if (counted) continue;
+		if (!havecov) { localcov = fitcovariance(); havecov = true; }
+		// pseudo-determinant: the product of the non-zero eigenvalues; Math.Pow(2 pi, -6 / 2) with integer division
+		Matrix6 V;
+		std::array<double, 6> vals;
+		detail::SymEig6(localcov, vals, V);
+		double lmax = 0, pdet = 1;
+		bool any = false;
+		for (double x : vals) lmax = std::max(lmax, std::fabs(x));
+		for (double x : vals) if (std::fabs(x) > 6 * 2.220446049250313e-16 * lmax) { pdet *= std::fabs(x); any = true; }
+		if (!any) pdet = 0;
+		const double logmultiplier = std::log(std::pow(2 * 3.14159265358979323846, -3.0)) - 0.5 * std::log(pdet);
+		components.push_back(PoseComponent{std::exp(values[a] - logmultiplier), poses[a], localcov});
+	}
+	return components;
+}
+}  // namespace detail
+
 // ≙ LoopyPHDNavigator.GuidedFitMixture (:777-852): see monorfs_amd/loopy.py for the walk-through; all guesses climb side
 // by side, the covariance is fitted once at pose0 (the reference's `maxpose` never moves).
 inline std::vector<PoseComponent> GuidedFitMixture(PHDNavigator& nav, double visionfocal, const Odometry& pose0,
@@ -446,48 +494,127 @@ inline std::vector<PoseComponent> GuidedFitMixture(PHDNavigator& nav, double vis
 	if (emptyspace) *emptyspace = v[0];
 	std::vector<Odometry> climbing;
 	for (size_t g = 0; g < guesses.size(); g++) if (!(v[1 + g] - v[0] < 0)) climbing.push_back(guesses[g]);
-	std::vector<PoseComponent> components;
-	if (climbing.empty()) return components;
+	if (climbing.empty()) return {};
 	std::vector<double> values;
 	const std::vector<Odometry> poses = LogLikeGradientAscent(nav, climbing, measurements, jmap, linearpoint, values, maxbatch, averagemode, 1e-2, 10, resident, maxiterations);
-	bool havecov = false;
-	Matrix6 localcov{};
-	auto pinvquad = [](const Matrix6& cov, const Odometry& d) {   // d' pinv(cov) d
-		Matrix6 V;
-		std::array<double, 6> vals;
-		detail::SymEig6(cov, vals, V);
-		double lmax = 0, q = 0;
-		for (double x : vals) lmax = std::max(lmax, std::fabs(x));
-		for (int e = 0; e < 6; e++) {
-			if (!(std::fabs(vals[e]) > 1e-15 * lmax)) continue;
-			double proj = 0;
-			for (int i = 0; i < 6; i++) proj += V[i * 6 + e] * d[i];
-			q += proj * proj / vals[e];
+	return detail::MixtureOf(poses, values, [&]() { return LogLikeFitCovariance(nav, pose0, measurements, jmap, linearpoint, averagemode); });
+}
+
+// GuidedFitMixture(..., resident = true) for many frames at once (≙ the Parallel.For of UpdateMessagesFromMap, :525-551): frame i
+// has pose0s[i], measurementsets[i], maps[i] and linearpoints[i]; returns the mixtures, emptyspaces[i] the value far from
+// everything. The guesses of every frame are made on the host as there; then THREE device calls serve all frames
+// (PHDNavigator::QuasiSetLogLikelihoodMulti, QuasiAscentMulti, QuasiSetLogLikelihoodGradientMulti): the far pose and the guesses
+// of every frame, the climb of every surviving guess, the 12 Hessian poses at pose0 of every frame that kept a guess. The dedupe
+// and the weights stay per frame on the host. maxbatch: the handle's max_particles. monorfs_amd/loopy.py has the Python twin.
+inline std::vector<std::vector<PoseComponent>> GuidedFitMixtures(PHDNavigator& nav, double visionfocal, const std::vector<Odometry>& pose0s,
+                                                                 const std::vector<std::vector<PixelRangeMeasurement>>& measurementsets,
+                                                                 const std::vector<Map>& maps, const std::vector<Pose3D>& linearpoints, int maxbatch,
+                                                                 std::vector<double>* emptyspaces = nullptr, int averagemode = 0, int maxiterations = 0)
+{
+	const size_t T = pose0s.size();
+	std::vector<PHDNavigator::QuasiProblem> problems(T);
+	std::vector<std::vector<Odometry>> guesses(T);
+	std::vector<size_t> at(T);
+	std::vector<Pose3D> first;
+	std::vector<int> which;
+	const Pose3D infpose = PoseAdd(Pose3D{0, 0, 0, 1, 0, 0, 0}, Odometry{1e5, 1e5, 1e5, 1e5, 1e5, 1e5});
+	for (size_t i = 0; i < T; i++) {
+		const Pose3D initpose = PoseAdd(linearpoints[i], pose0s[i]);
+		problems[i].Landmarks = BestMapEstimate(maps[i]);
+		problems[i].Measurements = measurementsets[i];
+		problems[i].LinearPoint = linearpoints[i];
+		guesses[i] = {pose0s[i]};
+		for (const auto& landmark : problems[i].Landmarks) {
+			for (const auto& measurement : measurementsets[i]) {
+				const Pose3D guess = FitToMeasurement(visionfocal, initpose, measurement, landmark);
+				const Odometry d = PoseSubtract(guess, initpose);
+				double sq = 0;
+				for (double x : d) sq += x * x;
+				if (sq < 0.5 * 0.5) guesses[i].push_back(PoseSubtract(guess, linearpoints[i]));
+			}
 		}
-		return q;
-	};
-	for (size_t a = 0; a < poses.size(); a++) {
-		bool counted = false;
-		for (const PoseComponent& c : components) {
-			Odometry d;
-			for (int t = 0; t < 6; t++) d[t] = c.mean[t] - poses[a][t];
-			if (std::sqrt(std::max(0.0, pinvquad(c.covariance, d))) < 0.1) { counted = true; break; }
-		}
-		if (counted) continue;
-		if (!havecov) { localcov = LogLikeFitCovariance(nav, pose0, measurements, jmap, linearpoint, averagemode); havecov = true; }
-		// pseudo-determinant: the product of the non-zero eigenvalues; Math.Pow(2 pi, -6 / 2) with integer division
-		Matrix6 V;
-		std::array<double, 6> vals;
-		detail::SymEig6(localcov, vals, V);
-		double lmax = 0, pdet = 1;
-		bool any = false;
-		for (double x : vals) lmax = std::max(lmax, std::fabs(x));
-		for (double x : vals) if (std::fabs(x) > 6 * 2.220446049250313e-16 * lmax) { pdet *= std::fabs(x); any = true; }
-		if (!any) pdet = 0;
-		const double logmultiplier = std::log(std::pow(2 * 3.14159265358979323846, -3.0)) - 0.5 * std::log(pdet);
-		components.push_back(PoseComponent{std::exp(values[a] - logmultiplier), poses[a], localcov});
+		at[i] = first.size();
+		first.push_back(infpose);
+		for (const Odometry& g : guesses[i]) first.push_back(PoseAdd(linearpoints[i], g));
+		which.insert(which.end(), 1 + guesses[i].size(), (int) i);
 	}
-	return components;
+	std::vector<std::vector<PoseComponent>> results(T);
+	if (emptyspaces) emptyspaces->assign(T, 0.0);
+	if (T == 0) return results;
+	const std::vector<double> v = nav.QuasiSetLogLikelihoodMulti(problems, first, which, maxbatch);
+	std::vector<Odometry> climbing;
+	std::vector<int> owner;
+	for (size_t i = 0; i < T; i++) {
+		if (emptyspaces) (*emptyspaces)[i] = v[at[i]];
+		for (size_t g = 0; g < guesses[i].size(); g++) {
+			if (!(v[at[i] + 1 + g] - v[at[i]] < 0)) { climbing.push_back(guesses[i][g]); owner.push_back((int) i); }
+		}
+	}
+	if (climbing.empty()) return results;
+	const PHDNavigator::AscentResult r = nav.QuasiAscentMulti(problems, climbing, owner, std::max(1, maxbatch / PHD_ASCENT_LINE), averagemode,
+	                                                          maxiterations > 0 ? maxiterations : ResidentIterationBound);
+	if (r.Capped && maxiterations <= 0) throw std::runtime_error("GuidedFitMixtures: the resident ascent is still climbing at its iteration bound");
+	std::vector<int> kept(owner);
+	kept.erase(std::unique(kept.begin(), kept.end()), kept.end());   // (owner is sorted: the frames in order)
+	const double eps = 1e-5;
+	std::vector<Pose3D> hposes;
+	std::vector<int> hwhich;
+	for (int i : kept) {   // the 12 poses of LogLikeFitCovariance at pose0
+		for (int t = 0; t < 6; t++) {
+			for (double sign : {1.0, -1.0}) {
+				Odometry d = pose0s[i];
+				d[t] += sign * eps;
+				hposes.push_back(PoseAdd(linearpoints[i], d));
+				hwhich.push_back(i);
+			}
+		}
+	}
+	std::vector<std::array<double, 6>> g;
+	nav.QuasiSetLogLikelihoodGradientMulti(problems, hposes, hwhich, g, maxbatch, averagemode);
+	for (size_t k = 0; k < kept.size(); k++) {
+		Matrix6 H;
+		for (int t = 0; t < 6; t++) {
+			for (int c = 0; c < 6; c++) H[t * 6 + c] = (g[k * 12 + 2 * t][c] - g[k * 12 + 2 * t + 1][c]) / (2 * eps);
+		}
+		const Matrix6 cov = HessianToCovariance(H);
+		std::vector<Odometry> poses;
+		std::vector<double> values;
+		for (size_t e = 0; e < owner.size(); e++) if (owner[e] == kept[k]) { poses.push_back(r.Poses[e]); values.push_back(r.Values[e]); }
+		results[kept[k]] = detail::MixtureOf(poses, values, [&]() { return cov; });
+	}
+	return results;
+}
+
+// The device part of LoopyPHDNavigator.UpdateMessagesFromMap (:511-552): LeaveOneOutMaps, then GuidedFitMixtures over the frames
+// < to that have measurements, each against the map it was left out of. A frame without measurements has an empty mixture and
+// the empty-space value 0 (:527-530). The temperature term and the fusions stay with the caller.
+inline std::vector<std::vector<PoseComponent>> MapMessageMixtures(PHDNavigator& nav, double visionfocal, const std::vector<std::pair<double, Pose3D>>& trajectory,
+                                                                  const std::vector<std::pair<double, std::vector<PixelRangeMeasurement>>>& factors,
+                                                                  const std::vector<Odometry>& pose0s, const std::vector<Pose3D>& linearpoints, int to,
+                                                                  int maxparticles, std::vector<double>* emptyspaces = nullptr, int averagemode = 0)
+{
+	to = std::max(0, std::min((int) trajectory.size(), to));
+	std::vector<int> indices(to);
+	for (int i = 0; i < to; i++) indices[i] = i;
+	const std::vector<Map> maps = LeaveOneOutMaps(nav, trajectory, factors, indices, to, maxparticles);
+	std::vector<int> seen;
+	std::vector<Odometry> p0;
+	std::vector<std::vector<PixelRangeMeasurement>> zs;
+	std::vector<Map> models;
+	std::vector<Pose3D> lins;
+	for (int i = 0; i < to; i++) {
+		if (factors[i].second.empty()) continue;
+		seen.push_back(i); p0.push_back(pose0s[i]); zs.push_back(factors[i].second); models.push_back(maps[i]); lins.push_back(linearpoints[i]);
+	}
+	std::vector<double> empties;
+	const std::vector<std::vector<PoseComponent>> fits = GuidedFitMixtures(nav, visionfocal, p0, zs, models, lins, maxparticles, &empties, averagemode);
+	std::vector<std::vector<PoseComponent>> out(to);
+	if (emptyspaces) emptyspaces->assign(to, 0.0);
+	for (size_t k = 0; k < seen.size(); k++) {
+		out[seen[k]] = fits[k];
+		if (emptyspaces) (*emptyspaces)[seen[k]] = empties[k];
+	}
+	return out;
 }
 
 }  // namespace monorfs

@@ -263,6 +263,65 @@ public:
 		return out;
 	}
 
+	// What differs between the frames of LoopyPHDNavigator.UpdateMessagesFromMap (:525-551): a problem of the calls below
+	struct QuasiProblem {
+		std::vector<std::array<double, 3>> Landmarks;
+		std::vector<PixelRangeMeasurement> Measurements;
+		Pose3D                             LinearPoint{0, 0, 0, 1, 0, 0, 0};
+	};
+
+	// QuasiAscent for the estimates of many problems in the same launches (phd_quasi_ascent_multi): estimate e starts at
+	// initial[e] and is searched against problems[problem[e]]; every estimate bit for bit as from QuasiAscent with its problem
+	// alone. A C call takes problems of one measurement-block class (<= 64, 65..128, 129..256 measurements) and maxestimates
+	// estimates: the estimates are split by class and chunked, the results come back in the caller's order.
+	AscentResult QuasiAscentMulti(const std::vector<QuasiProblem>& problems, const std::vector<std::array<double, 6>>& initial,
+	                              const std::vector<int>& problem, int maxestimates, int averagemode = 0, int maxiterations = 1000,
+	                              int rounditerations = 0, bool withhessians = false)
+	{
+		const size_t n = initial.size();
+		checkProblems(problems, problem, n);
+		AscentResult out;
+		out.Poses.resize(n); out.Values.resize(n); out.Iterations.resize(n);
+		if (withhessians) out.Hessians.resize(n);
+		for (const std::vector<int>& idx : multiCalls(problems, problem, maxestimates)) {
+			const PackedProblems pk = packProblems(problems, problem, idx, true);
+			const size_t k = idx.size();
+			std::vector<std::array<double, 6>> start(k), poses(k);
+			std::vector<double> values(k);
+			std::vector<int32_t> iterations(k);
+			std::vector<std::array<double, 36>> hessians(withhessians ? k : 0);
+			for (size_t j = 0; j < k; j++) start[j] = initial[idx[j]];
+			const int rc = phd_quasi_ascent_multi(nav_, (int) pk.lmoff.size() - 1, pk.lmoff.data(), pk.lm.empty() ? nullptr : pk.lm[0].data(),
+			                                      pk.zoff.data(), pk.z.empty() ? nullptr : pk.z[0].data(), pk.lin[0].data(), start[0].data(),
+			                                      pk.which.data(), (int) k, averagemode, maxiterations, rounditerations, poses[0].data(),
+			                                      values.data(), iterations.data(), withhessians ? hessians[0].data() : nullptr);
+			if (rc == PHD_ERR_CAPACITY) out.Capped = true;
+			else check(rc);
+			for (size_t j = 0; j < k; j++) {
+				out.Poses[idx[j]] = poses[j]; out.Values[idx[j]] = values[j]; out.Iterations[idx[j]] = iterations[j];
+				if (withhessians) out.Hessians[idx[j]] = hessians[j];
+			}
+		}
+		return out;
+	}
+
+	// QuasiSetLogLikelihood for poses of many problems in one launch (phd_quasi_set_loglik_multi): pose i against
+	// problems[problem[i]], at most maxposes (<= the handle's max_particles) a call
+	std::vector<double> QuasiSetLogLikelihoodMulti(const std::vector<QuasiProblem>& problems, const std::vector<Pose3D>& poses,
+	                                               const std::vector<int>& problem, int maxposes)
+	{
+		return quasiBatchMulti(problems, poses, problem, maxposes, 0, nullptr);
+	}
+
+	// ... with the gradients (phd_quasi_set_loglik_multi with gradients6)
+	std::vector<double> QuasiSetLogLikelihoodGradientMulti(const std::vector<QuasiProblem>& problems, const std::vector<Pose3D>& poses,
+	                                                       const std::vector<int>& problem, std::vector<std::array<double, 6>>& gradients,
+	                                                       int maxposes, int averagemode = 0)
+	{
+		gradients.assign(poses.size(), std::array<double, 6>{});
+		return quasiBatchMulti(problems, poses, problem, maxposes, averagemode, &gradients);
+	}
+
 	// KinectMeasurer's current depth frame (phd_set_depth_map): `depth` row-major [height][width] (the reference's
 	// float[ResX][ResY] frame transposed), used by every step until the next call; an empty vector switches it off
 	void setDepthMap(const std::vector<float>& depth, int width, int height)
@@ -378,6 +437,85 @@ private:
 	void check(int status)
 	{
 		if (status != PHD_OK) throw PhdError(status, phd_last_error(nav_));
+	}
+
+	// ---- the calls over many problems: which items go into which C call, and a call's problem table
+	struct PackedProblems {
+		std::vector<int32_t>               lmoff, zoff, which;   // offsets of the problems a call names; its items' problems, renumbered
+		std::vector<std::array<double, 3>> lm, z;                // the pools
+		std::vector<Pose3D>                lin;
+	};
+
+	static int blockClass(size_t m) { return m == 0 ? 0 : (m <= 64 ? 1 : (m <= 128 ? 2 : 4)); }   // 0: fits any class
+
+	static void checkProblems(const std::vector<QuasiProblem>& problems, const std::vector<int>& problem, size_t n)
+	{
+		bool ok = problem.size() == n;
+		for (int q : problem) ok = ok && q >= 0 && (size_t) q < problems.size();
+		if (!ok) throw std::invalid_argument("one problem index in [0, problems.size()) per estimate or pose");
+	}
+
+	// lists of item indices, each of one block class and at most percall long, the caller's order kept within a call; the items of
+	// problems without measurements ride with the first class that has any
+	static std::vector<std::vector<int>> multiCalls(const std::vector<QuasiProblem>& problems, const std::vector<int>& problem, int percall)
+	{
+		const size_t chunk = (size_t) (percall > 0 ? percall : 1);
+		int first = 0;
+		for (int cls : {4, 2, 1}) for (int q : problem) if (blockClass(problems[q].Measurements.size()) == cls) first = cls;
+		if (!first) first = 1;
+		std::vector<std::vector<int>> calls;
+		for (int cls : {1, 2, 4}) {
+			std::vector<int> idx;
+			for (size_t i = 0; i < problem.size(); i++) {
+				const int c = blockClass(problems[problem[i]].Measurements.size());
+				if ((c ? c : first) == cls) idx.push_back((int) i);
+			}
+			for (size_t s = 0; s < idx.size(); s += chunk) calls.emplace_back(idx.begin() + s, idx.begin() + std::min(idx.size(), s + chunk));
+		}
+		return calls;
+	}
+
+	static PackedProblems packProblems(const std::vector<QuasiProblem>& problems, const std::vector<int>& problem, const std::vector<int>& idx, bool withlin)
+	{
+		PackedProblems pk;
+		std::vector<int> renum(problems.size(), -1);
+		std::vector<int> used;
+		for (int i : idx) if (renum[problem[i]] < 0) { renum[problem[i]] = 0; used.push_back(problem[i]); }
+		std::sort(used.begin(), used.end());
+		pk.lmoff.push_back(0); pk.zoff.push_back(0);
+		for (size_t k = 0; k < used.size(); k++) {
+			const QuasiProblem& p = problems[used[k]];
+			renum[used[k]] = (int) k;
+			pk.lm.insert(pk.lm.end(), p.Landmarks.begin(), p.Landmarks.end());
+			pk.z.insert(pk.z.end(), p.Measurements.begin(), p.Measurements.end());
+			pk.lmoff.push_back((int32_t) pk.lm.size()); pk.zoff.push_back((int32_t) pk.z.size());
+			if (withlin) pk.lin.push_back(p.LinearPoint);
+		}
+		for (int i : idx) pk.which.push_back(renum[problem[i]]);
+		return pk;
+	}
+
+	std::vector<double> quasiBatchMulti(const std::vector<QuasiProblem>& problems, const std::vector<Pose3D>& poses, const std::vector<int>& problem,
+	                                    int maxposes, int averagemode, std::vector<std::array<double, 6>>* gradients)
+	{
+		checkProblems(problems, problem, poses.size());
+		std::vector<double> out(poses.size());
+		for (const std::vector<int>& idx : multiCalls(problems, problem, maxposes)) {
+			const PackedProblems pk = packProblems(problems, problem, idx, false);
+			const size_t k = idx.size();
+			std::vector<Pose3D> at(k);
+			std::vector<double> values(k);
+			std::vector<std::array<double, 6>> grad(gradients ? k : 0);
+			for (size_t j = 0; j < k; j++) at[j] = poses[idx[j]];
+			check(phd_quasi_set_loglik_multi(nav_, (int) pk.lmoff.size() - 1, pk.lmoff.data(), pk.lm.empty() ? nullptr : pk.lm[0].data(),
+			                                 pk.zoff.data(), pk.z.empty() ? nullptr : pk.z[0].data(), at[0].data(), pk.which.data(), (int) k,
+			                                 averagemode, values.data(), gradients ? grad[0].data() : nullptr));
+			for (size_t j = 0; j < k; j++) {
+				out[idx[j]] = values[j];
+				if (gradients) (*gradients)[idx[j]] = grad[j];
+			}
+		}
+		return out;
 	}
 
 	static Trajectories trajectories(size_t n, int L, const double* t, const double* x, const int32_t* s)

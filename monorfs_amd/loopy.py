@@ -273,27 +273,122 @@ def GuidedFitMixture(nav, pose0, measurements, model, linearpoint, average_mode=
     first = _values(nav, z, jmap, np.array([infpose] + [pose3d_add(lin, g) for g in guesses]))
     emptyspace = first[0]
     climbing = [g for g, v in zip(guesses, first[1:]) if not (v - emptyspace < 0)]
-    components = []
     if not climbing:
-        return emptyspace, components
+        return emptyspace, []
     poses, values = LogLikeGradientAscent(nav, np.array(climbing), z, jmap, lin, average_mode, resident, max_iterations)
-    localcov = None
+    return emptyspace, _mixture_of(poses, values, lambda: LogLikeFitCovariance(nav, pose0, z, jmap, lin, average_mode))
+
+
+def _mixture_of(poses, values, localcov):
+    """the tail of GuidedFitMixture (:825-850): maxima in order, one within Mahalanobis 0.1 of an earlier component dropped,
+    every component with the covariance fitted at pose0 (`localcov`: a callable, evaluated on first need)"""
+    components = []
+    cov = None
     for localpose, localmax in zip(poses, values):
         counted = False
-        for _, mean, cov in components:
+        for _, mean, c in components:
             diff = mean - localpose
-            if math.sqrt(max(0.0, diff @ np.linalg.pinv(cov) @ diff)) < 0.1:
+            if math.sqrt(max(0.0, diff @ np.linalg.pinv(c) @ diff)) < 0.1:
                 counted = True
                 break
         if counted:
             continue
-        if localcov is None:
-            localcov = LogLikeFitCovariance(nav, pose0, z, jmap, lin, average_mode)
+        if cov is None:
+            cov = localcov()
         # Math.Pow(2 pi, -localpose.Length / 2): integer division, exponent -3
         with np.errstate(divide="ignore"):
-            logmultiplier = math.log((2 * math.pi) ** (-(OdoSize // 2))) - 0.5 * np.log(_pseudo_determinant(localcov))
-        components.append((math.exp(localmax - logmultiplier), localpose, localcov))
-    return emptyspace, components
+            logmultiplier = math.log((2 * math.pi) ** (-(OdoSize // 2))) - 0.5 * np.log(_pseudo_determinant(cov))
+        components.append((math.exp(localmax - logmultiplier), localpose, cov))
+    return components
+
+
+def GuidedFitMixtures(nav, pose0s, measurement_sets, models, linearpoints, average_mode=0, max_iterations=None):
+    """GuidedFitMixture(..., resident=True) for many frames at once (≙ the Parallel.For of UpdateMessagesFromMap, :525-551):
+    frame i has the initial linear pose pose0s[i], the measurements measurement_sets[i], the map models[i] = (w, mean, cov) and
+    the linearisation pose linearpoints[i]. Returns the list of (emptyspace, components), frame i's exactly what
+    GuidedFitMixture(nav, pose0s[i], measurement_sets[i], models[i], linearpoints[i], average_mode, True, max_iterations) gives.
+
+    The guesses of every frame are made on the host as there. Then THREE device calls serve all frames (PHDNavigator's
+    QuasiSetLogLikelihoodMulti, QuasiAscentMulti, QuasiSetLogLikelihoodGradientMulti): the far pose and the guesses of every
+    frame, the climb of every surviving guess of every frame, the 12 Hessian poses at pose0 of every frame that kept a guess.
+    The dedupe and the weights stay per frame on the host. A `nav` without the multi methods takes the per-frame calls: that
+    fallback states what the three calls mean."""
+    T = len(pose0s)
+    if not hasattr(nav, "QuasiAscentMulti"):
+        resident = hasattr(nav, "QuasiAscent")   # (the oracle stub has the batch calls alone: the host drives its loop)
+        return [GuidedFitMixture(nav, pose0s[i], measurement_sets[i], models[i], linearpoints[i], average_mode, resident, max_iterations) for i in range(T)]
+    identity = np.array([0, 0, 0, 1.0, 0, 0, 0])
+    infpose = pose3d_add(identity, np.full(OdoSize, 1e5))
+    frames, problems = [], []
+    poses7, which = [], []
+    for i in range(T):
+        pose0 = np.asarray(pose0s[i], float).reshape(OdoSize)
+        lin = np.asarray(linearpoints[i], float)
+        z = np.asarray(measurement_sets[i], float).reshape(-1, 3)
+        initpose = pose3d_add(lin, pose0)
+        jmap = best_map_estimate(models[i])
+        guesses = [pose0]
+        for landmark in jmap:
+            for measurement in z:
+                guess = fit_to_measurement(nav.params, initpose, measurement, landmark)
+                d = pose3d_subtract(guess, initpose)
+                if float(np.dot(d, d)) < 0.5 * 0.5:
+                    guesses.append(pose3d_subtract(guess, lin))
+        frames.append((pose0, lin, guesses, len(poses7)))
+        problems.append((jmap, z, lin))
+        poses7 += [infpose] + [pose3d_add(lin, g) for g in guesses]
+        which += [i] * (1 + len(guesses))
+    first = nav.QuasiSetLogLikelihoodMulti(problems, np.array(poses7).reshape(-1, 7), which) if T else np.zeros(0)
+    empties, climbing, owner = [], [], []
+    for i, (pose0, lin, guesses, at) in enumerate(frames):
+        emptyspace = first[at]
+        empties.append(emptyspace)
+        for g, v in zip(guesses, first[at + 1:at + 1 + len(guesses)]):
+            if not (v - emptyspace < 0):
+                climbing.append(g)
+                owner.append(i)
+    results = [(empties[i], []) for i in range(T)]
+    if not climbing:
+        return results
+    bound = ResidentIterationBound if max_iterations is None else int(max_iterations)
+    poses, values, _, capped = nav.QuasiAscentMulti(problems, np.array(climbing), owner, average_mode, max_iterations=bound)
+    if capped and max_iterations is None:
+        raise RuntimeError("GuidedFitMixtures: still climbing after %d iterations" % bound)
+    kept = sorted(set(owner))
+    eps = 1e-5
+    hposes, hwhich = [], []
+    for i in kept:   # the 12 poses of LogLikeFitCovariance at pose0 (which the reference never updates, :800, :839)
+        pose0, lin = frames[i][0], frames[i][1]
+        for t in range(OdoSize):
+            for sign in (1.0, -1.0):
+                d = pose0.copy()
+                d[t] += sign * eps
+                hposes.append(pose3d_add(lin, d))
+                hwhich.append(i)
+    _, g = nav.QuasiSetLogLikelihoodGradientMulti(problems, np.array(hposes), hwhich, average_mode)
+    g = g.reshape(len(kept), OdoSize, 2, OdoSize)
+    owner = np.asarray(owner)
+    for k, i in enumerate(kept):
+        mine = np.nonzero(owner == i)[0]
+        cov = HessianToCovariance((g[k, :, 0] - g[k, :, 1]) / (2 * eps))
+        results[i] = (empties[i], _mixture_of(poses[mine], values[mine], lambda cov=cov: cov))
+    return results
+
+
+def MapMessageMixtures(nav, trajectory, factors, pose0s, linearpoints, to=None, average_mode=0):
+    """The device part of LoopyPHDNavigator.UpdateMessagesFromMap (:511-552): LeaveOneOutMaps, then GuidedFitMixtures over the
+    frames < to that have measurements against the map each of them was left out of. Returns one (emptyspace, components) per
+    frame; a frame without measurements gives (0.0, []) (:527-530). The temperature term and the fusions stay with the caller.
+    pose0s[i] / linearpoints[i]: the initial linear pose and the linearisation pose of frame i."""
+    to = len(trajectory) if to is None else min(len(trajectory), to)
+    maps, _ = LeaveOneOutMaps(nav, trajectory, factors, to=to)
+    seen = [i for i in range(to) if len(np.asarray(factors[i][1], float).reshape(-1, 3)) > 0]
+    fits = GuidedFitMixtures(nav, [pose0s[i] for i in seen], [factors[i][1] for i in seen], [maps[i] for i in seen],
+                             [linearpoints[i] for i in seen], average_mode)
+    out = [(0.0, []) for _ in range(to)]
+    for i, fit in zip(seen, fits):
+        out[i] = fit
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- Filter / FilterMissing

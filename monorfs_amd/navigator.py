@@ -376,6 +376,117 @@ class PHDNavigator:
                 self._check(rc)
         return (poses, values, iters, capped, hess) if hessians else (poses, values, iters, capped)
 
+    # ------------------------------------------------------------------ many problems in one call (phd_ascent_multi.h)
+    @staticmethod
+    def _block_class(m):
+        """the measurement-block class of a problem with m measurements (0 fits any class: None)"""
+        return None if m == 0 else (1 if m <= 64 else (2 if m <= 128 else 4))
+
+    @staticmethod
+    def _problem_table(problems):
+        """[(landmarks, measurements[, linearpoint]), ...] as contiguous arrays"""
+        lms = [np.ascontiguousarray(p[0], np.float64).reshape(-1, 3) for p in problems]
+        zs = [np.ascontiguousarray(p[1], np.float64).reshape(-1, 3) for p in problems]
+        lins = [np.ascontiguousarray(p[2], np.float64).reshape(7) if len(p) > 2 else None for p in problems]
+        return lms, zs, lins
+
+    def _multi_calls(self, zs, problem, per_call):
+        """The C calls that serve the items (estimates or poses) `problem`[n]: lists of item indices, each of one block class and at
+        most per_call long, in the caller's order within a call. The items of problems without measurements ride with the first
+        class that has any."""
+        classes = [self._block_class(len(z)) for z in zs]
+        present = sorted({c for c in (classes[q] for q in problem) if c is not None}) or [1]
+        groups = {c: [] for c in present}
+        for i, q in enumerate(problem):
+            groups[classes[q] if classes[q] is not None else present[0]].append(i)
+        calls = []
+        for c in present:
+            calls += [groups[c][s:s + per_call] for s in range(0, len(groups[c]), per_call)]
+        return calls
+
+    @staticmethod
+    def _pack_problems(lms, zs, lins, used):
+        """offsets, pools and linearisation poses of the problems `used` (in that order), and the map old index -> new"""
+        lmoff = np.zeros(len(used) + 1, np.int32)
+        zoff = np.zeros(len(used) + 1, np.int32)
+        for k, q in enumerate(used):
+            lmoff[k + 1] = lmoff[k] + len(lms[q])
+            zoff[k + 1] = zoff[k] + len(zs[q])
+        lm = np.ascontiguousarray(np.concatenate([lms[q] for q in used] + [np.zeros((0, 3))]))
+        z = np.ascontiguousarray(np.concatenate([zs[q] for q in used] + [np.zeros((0, 3))]))
+        lin = np.ascontiguousarray([lins[q] for q in used]) if lins is not None else None
+        return lmoff, lm, zoff, z, lin, {q: k for k, q in enumerate(used)}
+
+    def QuasiAscentMulti(self, problems, initial, problem, average_mode=0, max_iterations=1000, round_iterations=0, hessians=False):
+        """QuasiAscent for the estimates of many problems in the same launches (phd_quasi_ascent_multi): problems is a list of
+        (landmarks, measurements, linearpoint), estimate e starts at initial[e] and is searched against problems[problem[e]].
+        Returns what QuasiAscent returns, every estimate bit for bit as from QuasiAscent with its problem alone. A C call takes
+        problems of one measurement-block class (<= 64, 65..128, 129..256 measurements) and max_particles // 16 estimates: the
+        estimates are split by class and chunked, each call is handed only the problems its estimates name, and the results
+        come back in the caller's order."""
+        lms, zs, lins = self._problem_table(problems)
+        initial = np.ascontiguousarray(initial, np.float64).reshape(-1, 6)
+        problem = [int(q) for q in np.asarray(problem).reshape(-1)]
+        n = len(initial)
+        if len(problem) != n or any(q < 0 or q >= len(problems) for q in problem):
+            raise ValueError("one problem index in [0, len(problems)) per estimate")
+        poses, values, iters = np.zeros((n, 6)), np.zeros(n), np.zeros(n, np.int32)
+        hess = np.zeros((n, 6, 6)) if hessians else None
+        capped = False
+        for idx in self._multi_calls(zs, problem, max(1, self.params.max_particles // self.ASCENT_LINE)):
+            used = sorted({problem[i] for i in idx})
+            lmoff, lm, zoff, z, lin, renum = self._pack_problems(lms, zs, lins, used)
+            k = len(idx)
+            start = np.ascontiguousarray(initial[idx])
+            which = np.array([renum[problem[i]] for i in idx], np.int32)
+            p, v, it = np.zeros((k, 6)), np.zeros(k), np.zeros(k, np.int32)
+            h = np.zeros((k, 6, 6)) if hessians else None
+            rc = self._lib.phd_quasi_ascent_multi(self._h, len(used), lmoff.ctypes.data_as(ip), _ptr(lm) if len(lm) else None,
+                                                  zoff.ctypes.data_as(ip), _ptr(z) if len(z) else None, _ptr(lin), _ptr(start),
+                                                  which.ctypes.data_as(ip), k, int(average_mode), int(max_iterations), int(round_iterations),
+                                                  _ptr(p), _ptr(v), it.ctypes.data_as(ip), _ptr(h) if hessians else None)
+            if rc == PHD_ERR_CAPACITY:
+                capped = True
+            else:
+                self._check(rc)
+            poses[idx], values[idx], iters[idx] = p, v, it
+            if hessians:
+                hess[idx] = h
+        return (poses, values, iters, capped, hess) if hessians else (poses, values, iters, capped)
+
+    def _quasi_batch_multi(self, problems, poses, problem, average_mode, gradient):
+        lms, zs, _ = self._problem_table(problems)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        problem = [int(q) for q in np.asarray(problem).reshape(-1)]
+        n = len(poses)
+        if len(problem) != n or any(q < 0 or q >= len(problems) for q in problem):
+            raise ValueError("one problem index in [0, len(problems)) per pose")
+        out, grad = np.zeros(n), (np.zeros((n, 6)) if gradient else None)
+        for idx in self._multi_calls(zs, problem, max(1, self.params.max_particles)):
+            used = sorted({problem[i] for i in idx})
+            lmoff, lm, zoff, z, _, renum = self._pack_problems(lms, zs, None, used)
+            k = len(idx)
+            at = np.ascontiguousarray(poses[idx])
+            which = np.array([renum[problem[i]] for i in idx], np.int32)
+            o, g = np.zeros(k), (np.zeros((k, 6)) if gradient else None)
+            self._check(self._lib.phd_quasi_set_loglik_multi(self._h, len(used), lmoff.ctypes.data_as(ip), _ptr(lm) if len(lm) else None,
+                                                             zoff.ctypes.data_as(ip), _ptr(z) if len(z) else None, _ptr(at),
+                                                             which.ctypes.data_as(ip), k, int(average_mode), _ptr(o), _ptr(g) if gradient else None))
+            out[idx] = o
+            if gradient:
+                grad[idx] = g
+        return (out, grad) if gradient else out
+
+    def QuasiSetLogLikelihoodMulti(self, problems, poses, problem):
+        """QuasiSetLogLikelihood for poses of many problems in one launch (phd_quasi_set_loglik_multi): problems is a list of
+        (landmarks, measurements[, linearpoint]), pose i is evaluated against problems[problem[i]]. One value per pose, bit for
+        bit QuasiSetLogLikelihood's with that problem alone; split by block class and chunked by max_particles."""
+        return self._quasi_batch_multi(problems, poses, problem, 0, False)
+
+    def QuasiSetLogLikelihoodGradientMulti(self, problems, poses, problem, average_mode=0):
+        """QuasiSetLogLikelihoodGradient for poses of many problems in one launch: (values[n], gradients[n][6])."""
+        return self._quasi_batch_multi(problems, poses, problem, average_mode, True)
+
     def LogLikeGradient(self, pose, measurements, landmarks, linearpoint):
         """≙ LoopyPHDNavigator.LogLikeGradient (LoopyPHDNavigator.cs:876-909): central differences (eps = 1e-5) of the
         quasi set log-likelihood at linearpoint.Add(pose +- eps e_i) — the 12 evaluations go to the device as one batch.
