@@ -76,6 +76,36 @@ struct Bank {
 #define SEL_RESMIX 5   // bank holding the mixtures of the last step's result (slots: the resampling sources)
 #define SEL_STRIDE 8
 
+// The roles of the next step, decided on the device at the end of a step — the single-handle one (rotate_roles, k_nr_slots,
+// k_nr_sources in phd_resample.h) and the sharded one (k_finish_sharded, phd_shard.h) alike, so the host never waits inside a
+// step and a single handle and the ranks of a sharded run rotate the same way. No mixture is copied:
+//   not resampled: the new state is the OUT bank                      -> (IN, OUT, TMP, INMIX) = (O, I, T, O), slots identity
+//   resampled    : small arrays of particle i <- OUT[src[i]] into TMP -> (IN, OUT, TMP, INMIX) = (T, I, O, O), slots src
+//   frozen       : roles and slots stay (benchmark steady state); RES / RESMIX say where the result is (slots: src)
+// BankRoles: the roles of this step as its kernels read them (with whatever else they load first: one trip to memory).
+struct BankRoles { int in, out, tmp, inmix; };
+
+__device__ __forceinline__ BankRoles roles_now(const int* sel) { return BankRoles{sel[SEL_IN], sel[SEL_OUT], sel[SEL_TMP], sel[SEL_INMIX]}; }
+
+// (one thread of the launch)
+__device__ __forceinline__ void next_roles(const BankRoles& r, int* sel_next, int resampled, int frozen)
+{
+	const int I = r.in, O = r.out, T = r.tmp, X = r.inmix;
+	if (frozen)         { sel_next[SEL_IN] = I; sel_next[SEL_OUT] = O; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = X; }
+	else if (resampled) { sel_next[SEL_IN] = T; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = O; sel_next[SEL_INMIX] = O; }
+	else                { sel_next[SEL_IN] = O; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = O; }
+	sel_next[SEL_RES]    = resampled ? T : O;
+	sel_next[SEL_RESMIX] = O;
+}
+
+// A kernel of the step raised a flag (emit capacity, landmark scratch; a failed migration): what it wrote into the OUT bank is
+// not a valid state. The step is dropped as a whole — the roles stay, nothing of the current state was touched — and the host
+// finds the flag at its next phd_sync. (The first SEL_STRIDE threads of one workgroup.)
+__device__ __forceinline__ void keep_roles(const int* sel, int* sel_next, int tid)
+{
+	if (tid < SEL_STRIDE) sel_next[tid] = sel[tid];
+}
+
 struct StepBufs {
 	int P;          // particles of this handle
 	int p0;         // first particle of this launch (a step may be split into sub-ranges on concurrent streams)

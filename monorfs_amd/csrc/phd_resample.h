@@ -1,11 +1,17 @@
-// phd_resample.h — k_normalise_resample: PHDNavigator.cs:343-358 (normalise, BestParticle),
-// :768-777 (ParticleDepleted) and :724-760 (ResampleParticles) on the whole weight vector (all
-// ranks' particles when sharded). One workgroup of 1024 threads.
+// phd_resample.h — the end of every step: PHDNavigator.cs:343-358 (normalise, BestParticle), :768-777 (ParticleDepleted) and
+// :724-760 (ResampleParticles) on the whole weight vector (all ranks' particles when sharded), the gather of the resampled
+// particles' small arrays and the bank roles of the next step (next_roles, phd_kernels.h). Two implementations:
+//   k_normalise_resample: one workgroup of 256 / 512 / 1024 threads, a chunk of the vector per thread; the vector staged in LDS
+//     when it fits (up to 17 408 weights), walked in global memory beyond
+//   k_nr_sum, k_nr_stats, k_nr_slots, k_nr_sources: a grid of workgroups of 256 threads, one weight per thread, four launches
+// The grid takes the vectors of PHD_NR_GRID_MIN (default NR_GRID_MIN) to 65 536 weights, the one-workgroup kernel every other
+// length (all of them with PHD_NR_GRID_MIN=0): the length and that switch alone choose (launch_normalise). The two sum the weights
+// in different shapes, so every rank of a sharded run and a single handle holding all particles must run the same one.
 //
 // Systematic resampling in the reference is a sequential floating-point recurrence
 //     random = u / P;  for i: { while (random > 0 && k < P) random -= w[k++];  src[i] = k - 1;  random += 1 / P; }
 // whose indices must come out bit-exact. A GPU lane runs such a chain at ~100 cycles per step, so the
-// kernel gets the same indices in parallel by VERIFIED SPECULATION:
+// kernels get the same indices in parallel by VERIFIED SPECULATION:
 //   * in exact arithmetic the recurrence holds  random = T_i - S_k  with  T_i = fl(u/P) + i * fl(1/P)  and
 //     S_k = w_0 + ... + w_(k-1);  it stops iteration i at the first k with S_k >= T_i;
 //   * S (prefix sums) and T are evaluated in double-double arithmetic (error ~1e-30), in parallel;
@@ -17,11 +23,13 @@
 //     the recurrence's; otherwise one wave replays the recurrence literally (the fallback).
 // The result is bit-identical to the sequential code in both cases.
 //
-// Sum of the weights and of their squares: fixed-shape parallel tree (chunk per thread, then waves, then
-// the 16 wave totals), independent of the number of GPUs. (The reference sums sequentially; the last-bit
-// difference is far below the tolerance on particle weights, 1e-6.)
+// Sum of the weights and of their squares: fixed-shape parallel trees, independent of the number of GPUs. (The reference sums
+// sequentially; the last-bit difference is far below the tolerance on particle weights, 1e-6.)
 //   w (gw or the OUT bank): in: un-normalised weights, out: normalised weights, or 1/P after resampling
 //   src : [P] source slot of each particle (identity when not resampled);  info: [0] BestParticle, [1] resampled
+//
+// #pragma clang fp contract(off) is lexical: every function below that holds floating-point arithmetic carries its own (the
+// error-free transformations must not be fused, and a fused multiply-add anywhere moves a sum's last bit).
 #pragma once
 #include "phd_device.h"
 
@@ -73,9 +81,39 @@ __device__ __forceinline__ double dd_diff(dd a, dd b) {
 
 __device__ __forceinline__ double shfl_up_d(double v, int o) { return __shfl_up(v, o, 64); }
 
-// block-wide sums of a double, fixed order: thread partials -> wave butterflies -> wave 0 adds the 16 totals
+// inclusive double-double scan over the first `width` lanes of a wave (a power of two), by shuffles
+__device__ __forceinline__ dd dd_wave_scan(dd v, int lane, int width = 64)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+	for (int o = 1; o < width; o <<= 1) {
+		dd y = {shfl_up_d(v.hi, o), shfl_up_d(v.lo, o)};
+		if (lane >= o) v = dd_add(y, v);
+	}
+	return v;
+}
+
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+	return v;
+}
+
+// First maximum of a wave, smallest lane among equals: m <- the largest v of the lanes with `has` (whose other lanes bring
+// -INFINITY), -INFINITY when no lane holds one; returns the first lane that holds it (0 then).
+__device__ __forceinline__ int wave_first_max(double v, bool has, double& m)
+{
+	const double top = wave_max(v);
+	const unsigned long long bal = ballot64(has && v == top);
+	m = bal ? top : -INFINITY;
+	return bal ? __ffsll((long long) bal) - 1 : 0;
+}
+
+// block-wide sums of a double, fixed order: thread partials -> wave butterflies -> the wave totals in order
 __device__ __forceinline__ double block_sum_1024(double v, double* scratch16, int tid)
 {
+#pragma clang fp contract(off)
 	const int lane = tid & 63, wv = tid >> 6, nw = (int) (blockDim.x >> 6);
 	v = wave_sum(v);
 	__syncthreads();
@@ -84,6 +122,30 @@ __device__ __forceinline__ double block_sum_1024(double v, double* scratch16, in
 	double t = 0;
 	for (int q = 0; q < nw; q++) t += scratch16[q];
 	return t;
+}
+
+// ... of the grid kernels' 256 threads, from their four wave totals (without the loop's 0 + in front)
+__device__ __forceinline__ double block_sum_256(const double* s4)
+{
+#pragma clang fp contract(off)
+	return ((s4[0] + s4[1]) + s4[2]) + s4[3];
+}
+
+// ParticleDepleted (:768-777) from the sum of the squared weights, and what the caller forces (> 0: resample, < 0: do not)
+__device__ __forceinline__ bool resample_decided(double cum, double min_eff, int P, int force_resample)
+{
+#pragma clang fp contract(off)
+	bool depleted = (1.0 / cum < min_eff * P);   // :776
+	if (force_resample > 0) depleted = true;
+	if (force_resample < 0) depleted = false;
+	return depleted;
+}
+
+// B of the head comment: how far the recurrence's `random` can lie from T_i - S_k
+__device__ __forceinline__ double speculation_margin(int P, double gmax, double R0, double invP)
+{
+#pragma clang fp contract(off)
+	return 8.0 * P * 1.1102230246251565e-16 * (fmax(gmax, 0.0) + fabs(R0) + invP);
 }
 
 // T_i = fl(u / P) + i * fl(1 / P), exactly, as a double-double: what `random` is at slot i before anything is subtracted
@@ -113,24 +175,69 @@ __device__ __forceinline__ int slots_upto(dd x, double R0, double invP, int P, b
 	return n;
 }
 
+// The verified speculation for one particle k of weight wk: it takes the slots [lo, hi), lo = N(S_k), hi = N(S_(k+1)) with
+// N(x) = #{i : T_i <= x} (slots_upto).  S = S_k, Sb = S_(k+1);  hinat = N(Sb);  hi comes in as hinat, or P for the last particle
+// (the recurrence runs into P: whatever is left goes to it) and leaves clamped to lo.  Returns false unless the recurrence's
+// comparisons around the particle's slots are exact (B);  mybestw / mybesti: the thread's candidate for BestParticle, the first
+// slot of its heaviest particle (k ascending per thread, slots ascending with k: first maximum kept).
+// (k_nr_slots, one particle per thread, comes in with mybestw = -INFINITY: a particle with slots is its candidate. A NaN weight is
+// none, and has made the launch take the fallback already.)
+__device__ __forceinline__ bool claim_slots(dd S, dd Sb, int lo, int hinat, int k, double wk, double B, double R0, double invP,
+                                            int& hi, double& mybestw, int& mybesti)
+{
+#pragma clang fp contract(off)
+	bool ok = true;
+	if (hi < lo) { ok = false; hi = lo; }
+	if (hi > lo) {
+		// the last comparison that came out positive, at the particle's first slot (none for particle 0: `random` is
+		// u / P itself there, compared without any rounding)
+		if (k > 0) ok = ok && dd_diff(slot_target(lo, R0, invP), S) > B;
+		// the comparison that stopped the loop, at its last slot (none for the slots the last particle gets by k == P)
+		if (hinat > lo) ok = ok && dd_diff(Sb, slot_target(hinat - 1, R0, invP)) > B;
+		if (wk > mybestw) { mybestw = wk; mybesti = lo; }
+	}
+	return ok;
+}
+
+// The fallback: the recurrence itself (:724-760), by one wave, wave-uniform (weights through v_readlane, scalar control flow).
+// weight_at(q): the normalised weight of particle q as the speculation saw it.
+template <class W>
+__device__ __forceinline__ void replay_recurrence(int P, double u, int lane, int* src, int* info, W weight_at)
+{
+#pragma clang fp contract(off)
+	auto rl = [](double v, int l) {
+		int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+		return __hiloint2double(hi, lo);
+	};
+	const double invP = 1.0 / P;
+	double random = u / P, maxweight = 0;
+	int k = 0, best = 0, cb = 0;
+	double cur = (lane < P) ? weight_at(lane) : 0.0, prev = 0.0;
+	for (int i = 0; i < P; i++) {
+		while (k < P && __builtin_amdgcn_readfirstlane((int) (random > 0))) {
+			if (k >= cb + 64) { prev = cur; cb += 64; cur = (cb + lane < P) ? weight_at(cb + lane) : 0.0; }
+			random -= rl(cur, k - cb);
+			k++;
+		}
+		const int s = (k - 1 < 0) ? 0 : k - 1;   // u == 0 would index -1 in the reference: clamped
+		if (lane == 0) src[i] = s;
+		random += invP;
+		const double ws = (s >= cb) ? rl(cur, s - cb) : rl(prev, s - (cb - 64));
+		if (__builtin_amdgcn_readfirstlane((int) (ws > maxweight))) { maxweight = ws; best = i; }
+	}
+	if (lane == 0) { info[0] = best; info[1] = 1; }
+}
+
 // End of a single-handle step (sel_next != NULL), folded into the same launch: the resampled particles
-// (PHDNavigator.cs:740-741) and the bank roles of the next step, decided here from the resampling flag so the host never
-// waits inside a step. No mixture is copied:
-//   not resampled: the new state is the OUT bank                      -> (IN, OUT, TMP, INMIX) = (O, I, T, O), slots identity
-//   resampled    : small arrays of particle i <- OUT[src[i]] into TMP -> (IN, OUT, TMP, INMIX) = (T, I, O, O), slots src
-//   frozen       : roles and slots stay (benchmark steady state); RES / RESMIX say where the result is (slots: src)
-// Called by all 1024 threads after the source vector and the final weights are in global memory.
+// (PHDNavigator.cs:740-741) and the bank roles of the next step (next_roles, phd_kernels.h).
+// Called by all threads after the source vector and the final weights are in global memory.
+// (k_nr_sources' finish_slot gathers the same arrays one slot per thread with the weight 1 / P; the two stay apart: this loop's
+// two particles per trip and its weight from the OUT bank are what differs.)
 __device__ __forceinline__ void rotate_roles(const StepBufs& a, const int* src, int resampled, int* sel_next, int frozen,
                                              int* inslot, int tid)
 {
-	const int I = a.sel[SEL_IN], O = a.sel[SEL_OUT], T = a.sel[SEL_TMP], X = a.sel[SEL_INMIX];
-	if (tid == 0) {
-		if (frozen)         { sel_next[SEL_IN] = I; sel_next[SEL_OUT] = O; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = X; }
-		else if (resampled) { sel_next[SEL_IN] = T; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = O; sel_next[SEL_INMIX] = O; }
-		else                { sel_next[SEL_IN] = O; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = O; }
-		sel_next[SEL_RES]    = resampled ? T : O;
-		sel_next[SEL_RESMIX] = O;
-	}
+	const BankRoles now = roles_now(a.sel);
+	if (tid == 0) next_roles(now, sel_next, resampled, frozen);
 	const Bank bo = bank_of(a, SEL_OUT), bt = bank_of(a, SEL_TMP);
 	// two particles per thread and trip, their loads issued together: this tail is two dependent round trips to memory
 	// per trip in a single workgroup, nothing else
@@ -158,8 +265,16 @@ __device__ __forceinline__ void rotate_roles(const StepBufs& a, const int* src, 
 	}
 }
 
-// The body of the kernel's one workgroup.
-__device__ __forceinline__ void normalise_resample_body(const StepBufs& a, double* gw, int P, double min_eff, double u,
+// =================================================================================================================================
+// k_normalise_resample: ONE workgroup (launched with 1024 threads, or 256 / 512 for short weight vectors: the shape of the sums
+// depends on the vector length only). Its phases, in order — the PHD_STAMP marks between them are what scripts/stamps_nr.py
+// names —: stage the vector | sum | normalise, squares, best | decide, scan the chunk sums | the slots: per particle on the
+// staged vector, or per slot in global memory | BestParticle and the sources, or the fallback | reset the weights | the roles.
+// They stay one function over shared locals (the chunk, the LDS plan, W / lpos): cut into functions, the compiler built the
+// loops of this kernel differently (longer, more registers), and one workgroup alone on the device pays for that in full.
+// (A function apart from the kernel because it returns early — a dropped step, no resampling — in front of the diagnostic
+// build's timeline mark.)
+__device__ __forceinline__ void normalise_resample_workgroup(const StepBufs& a, double* gw, int P, double min_eff, double u,
                                                         int force_resample, int skip_normalise, int use_lds,
                                                         int* src, int* info, int* sel_next, int frozen, int* inslot,
                                                         double* lw /* LDS, [P] chunk-transposed when use_lds */)
@@ -181,11 +296,8 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 	const int flags_now = sel_next ? *a.flags : 0;
 	const int sel_out = a.sel[SEL_OUT];
 	if (tid == 0 && a.bigws_used && *a.bigws_used) *a.bigws_used = 0;   // the association slab is free again (every k_alpha_assoc of the step is over)
-	// A kernel of this step raised a flag (emit capacity, landmark scratch): what it wrote into the OUT bank is not a
-	// valid state. The step is dropped as a whole — the roles stay, nothing of the current state was touched — and the host
-	// finds the flag at its next phd_sync. (Every thread reads the same word, written by earlier launches.)
-	if (sel_next && flags_now != 0) {
-		if (tid < SEL_STRIDE) sel_next[tid] = a.sel[tid];
+	if (sel_next && flags_now != 0) {   // a dropped step (every thread reads the same word, written by earlier launches)
+		keep_roles(a.sel, sel_next, tid);
 		return;
 	}
 	double* gwp = gw ? gw : bank_of(a, SEL_OUT).weights;
@@ -248,14 +360,11 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 	const double cum = block_sum_1024(part2, s16, tid);
 	// arg-max with the smallest index among equals
 	{
-		double m = wmax;
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-		unsigned long long bal = ballot64(wmax == m && c0 < c1);
-		int firstl = bal ? __ffsll((long long) bal) - 1 : 0;
-		int idx = __shfl(imax, firstl, 64);
+		double m;
+		const int firstl = wave_first_max(wmax, c0 < c1, m);
+		const int idx = __shfl(imax, firstl, 64);
 		__syncthreads();
-		if (lane == 0) { s16b[wv] = bal ? m : -INFINITY; s_i16[wv] = idx; }
+		if (lane == 0) { s16b[wv] = m; s_i16[wv] = idx; }
 		__syncthreads();
 	}
 	double gmax = -INFINITY;
@@ -265,11 +374,7 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 	}
 	if (!(gmax > 0)) gbest = 0;   // maxweight starts at 0 and the comparison is strict (:347-353)
 	PHD_STAMP(3);
-	bool depleted = (1.0 / cum < min_eff * P);   // :776
-	if (force_resample > 0) depleted = true;
-	if (force_resample < 0) depleted = false;
-
-	if (!depleted) {   // uniform: every thread computed the same `cum`
+	if (!resample_decided(cum, min_eff, P, force_resample)) {   // uniform: every thread computed the same `cum`
 		if (tid == 0) { info[0] = gbest; info[1] = 0; }
 		for (int i = tid; i < P; i += nt) {
 			src[i] = i;
@@ -281,24 +386,13 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 
 	// ---- ResampleParticles (:724-760) by verified speculation
 	// exclusive double-double scan of the chunk sums: wave scan by shuffles, then the 16 wave totals
-	dd incl = chunk;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		dd y = {shfl_up_d(incl.hi, o), shfl_up_d(incl.lo, o)};
-		if (lane >= o) incl = dd_add(y, incl);
-	}
+	const dd incl = dd_wave_scan(chunk, lane);
 	__syncthreads();
 	if (lane == 63) { s16[wv] = incl.hi; s16b[wv] = incl.lo; }
 	__syncthreads();
 	dd woff;
 	{   // exclusive scan of the wave totals: lane q holds wave q's, every wave does the same four steps; its own offset is lane wv's
-		dd tot = (lane < nw) ? dd{s16[lane], s16b[lane]} : dd{0, 0};
-		dd inc = tot;
-#pragma unroll
-		for (int o = 1; o < 16; o <<= 1) {
-			dd y = {shfl_up_d(inc.hi, o), shfl_up_d(inc.lo, o)};
-			if (lane >= o) inc = dd_add(y, inc);
-		}
+		const dd inc = dd_wave_scan((lane < nw) ? dd{s16[lane], s16b[lane]} : dd{0, 0}, lane, 16);
 		woff = (wv == 0) ? dd{0, 0} : dd{__shfl(inc.hi, wv - 1, 64), __shfl(inc.lo, wv - 1, 64)};   // (wave-uniform index)
 	}
 	dd excl = dd_add(woff, incl);
@@ -311,7 +405,7 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 
 	PHD_STAMP(4);
 	const double R0 = u / P, invP = 1.0 / P;
-	const double B = 8.0 * P * 1.1102230246251565e-16 * (fmax(gmax, 0.0) + fabs(R0) + invP);
+	const double B = speculation_margin(P, gmax, R0, invP);
 	const int nchunks = (P + CH - 1) / CH;
 	bool   ok = !bad;
 	double mybestw = -INFINITY;
@@ -336,18 +430,9 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 			const double wk = lw[j * LS + tid];
 			const dd Sn = dd_add_d(S, wk);
 			const dd Sb = (j == cn - 1 && tid + 1 < nchunks) ? dd{s_pchi[tid + 1], s_pclo[tid + 1]} : Sn;   // S_(k+1) as the next chunk knows it
-			int hi = slots_upto(Sb, R0, invP, P, &settled);
-			const int hinat = hi;
-			if (k == P - 1) hi = P;        // the recurrence runs into P: whatever is left goes to the last particle
-			if (hi < lo) { ok = false; hi = lo; }
-			if (hi > lo) {
-				// the last comparison that came out positive, at the particle's first slot (none for particle 0: `random` is
-				// u / P itself there, compared without any rounding)
-				if (k > 0) ok = ok && dd_diff(slot_target(lo, R0, invP), S) > B;
-				// the comparison that stopped the loop, at its last slot (none for the slots the last particle gets by k == P)
-				if (hinat > lo) ok = ok && dd_diff(Sb, slot_target(hinat - 1, R0, invP)) > B;
-				if (wk > mybestw) { mybestw = wk; mybesti = lo; }   // k ascending per thread, slots ascending with k: first maximum kept
-			}
+			const int hinat = slots_upto(Sb, R0, invP, P, &settled);
+			int hi = (k == P - 1) ? P : hinat;
+			if (!claim_slots(S, Sb, lo, hinat, k, wk, B, R0, invP, hi, mybestw, mybesti)) ok = false;
 			cells[j * LS + tid] = make_int2(hi, 0);
 			S = Sn; lo = hi;
 		}
@@ -422,9 +507,7 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 	PHD_STAMP(5);
 	if (s_ok) {
 		// BestParticle = first slot whose source has the largest weight (:745-748)
-		double m = mybestw;
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+		const double m = wave_max(mybestw);
 		if (lane == 0) s16[wv] = m;
 		__syncthreads();
 		double gm = -INFINITY;
@@ -465,30 +548,9 @@ __device__ __forceinline__ void normalise_resample_body(const StepBufs& a, doubl
 		}
 	}
 	else if (wv == 0) {
-		// fallback: the recurrence itself, wave-uniform (weights through v_readlane, scalar control flow)
-		auto rl = [](double v, int l) {
-			int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-			return __hiloint2double(hi, lo);
-		};
 		// (the staged weights have given way to the cells: read from memory — still un-normalised there when this launch
 		// normalises, so divided again, by the same sum: the same bits)
-		auto wk = [&](int q) { return (use_lds && !skip_normalise) ? gwp[q] / nsum : gwp[q]; };
-		double random = u / P, maxweight = 0;
-		int k = 0, best = 0, cb = 0;
-		double cur = (lane < P) ? wk(lane) : 0.0, prev = 0.0;
-		for (int i = 0; i < P; i++) {
-			while (k < P && __builtin_amdgcn_readfirstlane((int) (random > 0))) {
-				if (k >= cb + 64) { prev = cur; cb += 64; cur = (cb + lane < P) ? wk(cb + lane) : 0.0; }
-				random -= rl(cur, k - cb);
-				k++;
-			}
-			int s = (k - 1 < 0) ? 0 : k - 1;   // u == 0 would index -1 in the reference: clamped
-			if (lane == 0) src[i] = s;
-			random += invP;
-			double ws = (s >= cb) ? rl(cur, s - cb) : rl(prev, s - (cb - 64));
-			if (__builtin_amdgcn_readfirstlane((int) (ws > maxweight))) { maxweight = ws; best = i; }
-		}
-		if (lane == 0) { info[0] = best; info[1] = 1; }
+		replay_recurrence(P, u, lane, src, info, [&](int q) { return (use_lds && !skip_normalise) ? gwp[q] / nsum : gwp[q]; });
 	}
 	__syncthreads();
 	PHD_STAMP(6);
@@ -510,14 +572,14 @@ __global__ __launch_bounds__(1024) void k_normalise_resample(const StepBufs a, d
 {
 	extern __shared__ __align__(16) double lw_nr[];   // [P] when use_lds
 	PHD_TL_BEGIN;
-	normalise_resample_body(a, gw, P, min_eff, u, force_resample, skip_normalise, use_lds, src, info, sel_next, frozen, inslot, lw_nr);
+	normalise_resample_workgroup(a, gw, P, min_eff, u, force_resample, skip_normalise, use_lds, src, info, sel_next, frozen, inslot, lw_nr);
 #ifdef PHD_STAMPS
 	if (threadIdx.x == 0 && a.stamps && a.stamp_kernel == 199) { a.stamps[8] = (double) tl0_; a.stamps[9] = (double) wall_clock64(); }
 #endif
 }
 
 // =================================================================================================================================
-// The same step over a GRID of workgroups (round 5), for weight vectors of NR_GRID_MIN entries and more — what every rank of a
+// The same step over a GRID of workgroups, for weight vectors of NR_GRID_MIN to 65 536 entries — what every rank of a
 // multi-GPU run resamples per step (config C8: 16 384 weights on each of 8 GPUs): one workgroup of 1024 threads spent 48 us on
 // them, bound by ONE compute unit's FP64 rate while 255 others idled. Here every thread owns ONE particle, a workgroup 256
 // consecutive ones, and what the whole vector must agree on meets between four launches (a dependent launch boundary costs
@@ -527,14 +589,13 @@ __global__ __launch_bounds__(1024) void k_normalise_resample(const StepBufs a, d
 //                 maximum, a negative / NaN weight seen, the double-double sum of its weights; per particle: the inclusive
 //                 double-double prefix inside its workgroup
 //   k_nr_slots    depleted? (PHDNavigator.cs:768-777); if not: identity sources, BestParticle, the roles. Else per particle the
-//                 slots it takes, [N(S_k), N(S_k+1)) — the verified speculation of the kernel above, one particle per thread —,
-//                 the margin tests, the candidate for BestParticle
+//                 slots it takes, [N(S_k), N(S_k+1)) — claim_slots, one particle per thread —, the candidate for BestParticle
 //   k_nr_sources  every slot finds its source by a sixteen-way search over the particles' upper slot bounds (non-decreasing), the weights
 //                 become 1 / P, the small arrays of the resampled particles are gathered, the roles rotate; one wave replays
 //                 the recurrence literally when a margin test failed (never seen outside the tests that force it)
 // The shape of every sum depends on the length of the vector only, as in the one-workgroup kernel: all ranks of a sharded run
-// and a single handle holding all particles get the same bits. (The two kernels' sums have different shapes — a thread's chunk
-// there, one weight per thread here —: which one runs is decided by the vector's length alone, too.)
+// and a single handle holding all particles get the same bits. (The two implementations' sums have different shapes — a thread's
+// chunk there, one weight per thread here.)
 #define NR_GRID_MIN 8192
 #define NR_STAT 8   // doubles per workgroup in the statistics block: sum, sum of squares, max, index of the max, bad, dd sum hi / lo, spare
 #define NR_SLOT 4   // ... in the slots block: ok, best weight, best slot, spare
@@ -555,12 +616,7 @@ __device__ __forceinline__ void nr_scan_groups(dd mine, int g, double* s_hi, dou
 {
 #pragma clang fp contract(off)
 	const int lane = tid & 63, wv = tid >> 6;
-	dd inc = mine;   // workgroup `tid`'s sum (zero beyond the last workgroup)
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		dd y = {shfl_up_d(inc.hi, o), shfl_up_d(inc.lo, o)};
-		if (lane >= o) inc = dd_add(y, inc);
-	}
+	const dd inc = dd_wave_scan(mine, lane);   // workgroup `tid`'s sum (zero beyond the last workgroup)
 	if (lane == 63) { s_hi[wv] = inc.hi; s_lo[wv] = inc.lo; }
 	__syncthreads();
 	dd incl = inc;
@@ -606,14 +662,14 @@ __global__ __launch_bounds__(256) void k_nr_sum(const StepBufs a, double* gw, in
 		if (k < world) gw[P + k] = graw[(size_t) k * (Pl + 1) + Pl];
 	}
 	else w = nr_weight(a, gw, k, k < P);
-	if (flags_now != 0) {   // a kernel of this step raised a flag: the step is dropped as a whole (see the body above)
-		if (g == 0 && tid < SEL_STRIDE) sel_next[tid] = a.sel[tid];
+	if (flags_now != 0) {   // a kernel of this step raised a flag: the step is dropped as a whole
+		if (g == 0) keep_roles(a.sel, sel_next, tid);
 		return;
 	}
 	double s = skip_normalise ? 0.0 : wave_sum(w);
 	if (lane == 0) s4[wv] = s;
 	__syncthreads();
-	if (tid == 0) nr.part[(size_t) g * NR_STAT] = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+	if (tid == 0) nr.part[(size_t) g * NR_STAT] = block_sum_256(s4);
 }
 
 __global__ __launch_bounds__(256) void k_nr_stats(const StepBufs a, double* gw, int P, int skip_normalise, int* sel_next, NrGrid nr)
@@ -631,7 +687,7 @@ __global__ __launch_bounds__(256) void k_nr_stats(const StepBufs a, double* gw, 
 		const double pv = wave_sum((tid < nr.G) ? nr.part[(size_t) tid * NR_STAT] : 0.0);
 		if (lane == 0) s4[wv] = pv;
 		__syncthreads();
-		const double sum = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+		const double sum = block_sum_256(s4);
 		nsum = (sum == 0) ? 1 : sum;
 		__syncthreads();   // (s4 is used again below)
 	}
@@ -642,23 +698,14 @@ __global__ __launch_bounds__(256) void k_nr_stats(const StepBufs a, double* gw, 
 		(gw ? gw : bank_of(a, SEL_OUT).weights)[k] = wk;
 	}
 	const bool bad = k < P && !(wk >= 0);
-	// sum of squares (:772-774), first maximum (:347-354)
+	// sum of squares (:772-774), first maximum (:347-354), inclusive double-double prefix inside the workgroup
 	const double sq = wave_sum(wk * wk);
-	double m = (k < P) ? wk : -INFINITY;
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-	const unsigned long long bal = ballot64(k < P && wk == m);
-	const int firstl = bal ? __ffsll((long long) bal) - 1 : 0;
-	// inclusive double-double prefix inside the workgroup
-	dd inc = {wk, 0};
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		dd y = {shfl_up_d(inc.hi, o), shfl_up_d(inc.lo, o)};
-		if (lane >= o) inc = dd_add(y, inc);
-	}
+	double m;
+	const int firstl = wave_first_max((k < P) ? wk : -INFINITY, k < P, m);
+	const dd inc = dd_wave_scan(dd{wk, 0}, lane);
 	__syncthreads();
 	if (bad) s_bad = 1;
-	if (lane == 0) { s4[wv] = sq; s4b[wv] = bal ? m : -INFINITY; s_i4[wv] = g * 256 + wv * 64 + firstl; }
+	if (lane == 0) { s4[wv] = sq; s4b[wv] = m; s_i4[wv] = g * 256 + wv * 64 + firstl; }
 	if (lane == 63) { s_hi[wv] = inc.hi; s_lo[wv] = inc.lo; }
 	__syncthreads();
 	dd off = {0, 0};
@@ -673,7 +720,7 @@ __global__ __launch_bounds__(256) void k_nr_stats(const StepBufs a, double* gw, 
 			if (s4b[q] > gm) { gm = s4b[q]; gi = s_i4[q]; }
 		}
 		double* o = nr.part + (size_t) g * NR_STAT;
-		o[1] = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+		o[1] = block_sum_256(s4);
 		o[2] = gm; o[3] = (double) gi; o[4] = (double) s_bad;
 	}
 }
@@ -702,16 +749,13 @@ __global__ __launch_bounds__(256) void k_nr_slots(const StepBufs a, double* gw, 
 		const double q1 = has ? st[1] : 0.0, q2 = has ? st[2] : -INFINITY, q3 = has ? st[3] : 0.0, q4 = has ? st[4] : 0.0;
 		gsum = has ? dd{st[5], st[6]} : dd{0, 0};
 		const double csum = wave_sum(q1);
-		double m = q2;
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-		const unsigned long long mb = ballot64(has && q2 == m);
-		const int fl = mb ? __ffsll((long long) mb) - 1 : 0;
+		double m;
+		const int fl = wave_first_max(q2, has, m);
 		const int gi = (int) __shfl(q3, fl, 64);
 		const unsigned long long bb = ballot64(q4 != 0.0);
-		if (lane == 0) { s_hi[wv] = csum; s_lo[wv] = mb ? m : -INFINITY; s_hilast[wv] = gi; s_bw[wv] = bb ? 1.0 : 0.0; }
+		if (lane == 0) { s_hi[wv] = csum; s_lo[wv] = m; s_hilast[wv] = gi; s_bw[wv] = bb ? 1.0 : 0.0; }
 		__syncthreads();
-		cum = ((s_hi[0] + s_hi[1]) + s_hi[2]) + s_hi[3];
+		cum = block_sum_256(s_hi);
 		gmax = -INFINITY; gbest = 0;
 		for (int w = 0; w < 4; w++) {
 			if (s_lo[w] > gmax) { gmax = s_lo[w]; gbest = s_hilast[w]; }   // first maximum: the workgroups in order
@@ -720,9 +764,7 @@ __global__ __launch_bounds__(256) void k_nr_slots(const StepBufs a, double* gw, 
 		__syncthreads();   // (the arrays are used again below)
 	}
 	if (!(gmax > 0)) gbest = 0;   // maxweight starts at 0 and the comparison is strict (:347-353)
-	bool depleted = (1.0 / cum < min_eff * P);   // :776
-	if (force_resample > 0) depleted = true;
-	if (force_resample < 0) depleted = false;
+	const bool depleted = resample_decided(cum, min_eff, P, force_resample);
 	if (g == 0 && tid == 0) nr.state[0] = depleted ? 1 : 0;
 	if (!depleted) {
 		if (g == 0 && tid == 0) { info[0] = gbest; info[1] = 0; }
@@ -730,23 +772,18 @@ __global__ __launch_bounds__(256) void k_nr_slots(const StepBufs a, double* gw, 
 			src[k] = k;
 			if (sel_next && !frozen) inslot[k] = k;
 		}
-		if (sel_next && g == 0 && tid == 0) {
-			const int I = a.sel[SEL_IN], O = a.sel[SEL_OUT], T = a.sel[SEL_TMP], X = a.sel[SEL_INMIX];
-			if (frozen) { sel_next[SEL_IN] = I; sel_next[SEL_OUT] = O; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = X; }
-			else        { sel_next[SEL_IN] = O; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = O; }
-			sel_next[SEL_RES] = O; sel_next[SEL_RESMIX] = O;
-		}
+		if (sel_next && g == 0 && tid == 0) next_roles(roles_now(a.sel), sel_next, 0, frozen);
 		return;
 	}
 	// ---- ResampleParticles (:724-760) by verified speculation, one particle per thread: particle k takes the slots
-	// [N(S_k), N(S_(k+1))), N(x) = #{i : T_i <= x} (see the kernel above). S_k = the workgroup's offset + the prefix of the lane
+	// [N(S_k), N(S_(k+1))) (claim_slots). S_k = the workgroup's offset + the prefix of the lane
 	// before; the numbers on the two sides of every boundary — between lanes, waves and workgroups — are the same numbers, so the
 	// ranges tile [0, P).
 	dd woff, wnext;
 	nr_scan_groups(gsum, g, s_hi, s_lo, tid, woff, wnext);
 	if (tid == 0) { s_ok = 1; s_best = 0x7fffffff; }
 	const double R0 = u / P, invP = 1.0 / P;
-	const double B = 8.0 * P * 1.1102230246251565e-16 * (fmax(gmax, 0.0) + fabs(R0) + invP);
+	const double B = speculation_margin(P, gmax, R0, invP);
 	bool ok = !bad, settled = true;
 	// S_(k+1); at the workgroup's last particle: what the NEXT workgroup starts from
 	const bool lastofgroup = tid == 255 && g + 1 < nr.G;
@@ -764,22 +801,13 @@ __global__ __launch_bounds__(256) void k_nr_slots(const StepBufs a, double* gw, 
 	double mybestw = -INFINITY;
 	int mybesti = 0x7fffffff;
 	if (live) {
-		if (hi < lo) { ok = false; hi = lo; }
-		if (hi > lo) {
-			// the last comparison that came out positive, at the particle's first slot (none for particle 0: `random` is u / P itself there)
-			if (k > 0) ok = ok && dd_diff(slot_target(lo, R0, invP), S) > B;
-			// the comparison that stopped the loop, at its last slot (none for the slots the last particle gets by k == P)
-			if (hinat > lo) ok = ok && dd_diff(Sb, slot_target(hinat - 1, R0, invP)) > B;
-			mybestw = wk; mybesti = lo;
-		}
+		if (!claim_slots(S, Sb, lo, hinat, k, wk, B, R0, invP, hi, mybestw, mybesti)) ok = false;
 		nr.hi[k] = hi;
 	}
 	ok = ok && settled;
 	if (!ok) s_ok = 0;
 	// BestParticle = first slot whose source has the largest weight (:745-748): the workgroup's candidate
-	double m = mybestw;
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+	const double m = wave_max(mybestw);
 	if (lane == 0) s_bw[wv] = m;
 	__syncthreads();
 	const double gmw = fmax(fmax(s_bw[0], s_bw[1]), fmax(s_bw[2], s_bw[3]));
@@ -813,10 +841,8 @@ __global__ __launch_bounds__(256) void k_nr_sources(const StepBufs a, double* gw
 		const bool has = tid < nr.G;
 		const double* r = nr.slotres + (size_t) (has ? tid : 0) * NR_SLOT;
 		const double r0 = has ? r[0] : 1.0, r1 = has ? r[1] : -INFINITY, r2 = has ? r[2] : 2147483647.0;
-		double m = r1;
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-		int bs = (has && r1 == m) ? (int) r2 : 0x7fffffff;   // the smallest slot among the candidates with the largest weight
+		const double m = wave_max(r1);
+		int bs = (has && r1 == m) ? (int) r2 : 0x7fffffff;   // the smallest SLOT among the candidates with the largest weight (not the first lane's)
 #pragma unroll
 		for (int o = 32; o > 0; o >>= 1) bs = min(bs, __shfl_xor(bs, o, 64));
 		const unsigned long long nb = ballot64(r0 == 0.0);
@@ -840,16 +866,10 @@ __global__ __launch_bounds__(256) void k_nr_sources(const StepBufs a, double* gw
 			if (!frozen) inslot[slot] = s_i;
 		}
 	};
-	auto roles = [&]() {
-		const int I = a.sel[SEL_IN], O = a.sel[SEL_OUT], T = a.sel[SEL_TMP], X = a.sel[SEL_INMIX];
-		if (frozen) { sel_next[SEL_IN] = I; sel_next[SEL_OUT] = O; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = X; }
-		else        { sel_next[SEL_IN] = T; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = O; sel_next[SEL_INMIX] = O; }
-		sel_next[SEL_RES] = T; sel_next[SEL_RESMIX] = O;
-	};
 	if (ok) {
 		if (g == 0 && tid == 0) {
 			info[0] = (gm > 0) ? best : 0; info[1] = 1;
-			if (sel_next) roles();
+			if (sel_next) next_roles(roles_now(a.sel), sel_next, 1, frozen);
 		}
 		// the source of slot i: the first particle whose upper slot bound lies beyond i (the bounds never decrease; the last is P)
 		// (sixteen ways per trip to memory — fifteen pivots requested together — instead of two: four trips at 16 384 weights,
@@ -888,39 +908,16 @@ __global__ __launch_bounds__(256) void k_nr_sources(const StepBufs a, double* gw
 		}
 		return;
 	}
-	// ---- fallback: the recurrence itself, by one wave (weights through v_readlane, scalar control flow); the weights are
-	// normalised in place already
+	// ---- fallback: one wave of the first workgroup replays the recurrence; the weights are normalised in place already
 	if (g != 0) return;
-	if (tid < 64) {
-		auto rl = [](double v, int l) {
-			int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-			return __hiloint2double(hi, lo);
-		};
-		const double invP = 1.0 / P;
-		double random = u / P, maxweight = 0;
-		int k = 0, bestslot = 0, cb = 0;
-		double cur = (lane < P) ? gwp[lane] : 0.0, prev = 0.0;
-		for (int s = 0; s < P; s++) {
-			while (k < P && __builtin_amdgcn_readfirstlane((int) (random > 0))) {
-				if (k >= cb + 64) { prev = cur; cb += 64; cur = (cb + lane < P) ? gwp[cb + lane] : 0.0; }
-				random -= rl(cur, k - cb);
-				k++;
-			}
-			const int sidx = (k - 1 < 0) ? 0 : k - 1;   // u == 0 would index -1 in the reference: clamped
-			if (lane == 0) src[s] = sidx;
-			random += invP;
-			const double ws = (sidx >= cb) ? rl(cur, sidx - cb) : rl(prev, sidx - (cb - 64));
-			if (__builtin_amdgcn_readfirstlane((int) (ws > maxweight))) { maxweight = ws; bestslot = s; }
-		}
-		if (lane == 0) { info[0] = bestslot; info[1] = 1; }
-	}
+	if (tid < 64) replay_recurrence(P, u, lane, src, info, [&](int q) { return gwp[q]; });
 	__threadfence_block();
 	__syncthreads();
 	for (int s = tid; s < P; s += 256) {
 		gwp[s] = 1.0 / P;
 		finish_slot(src[s], s);
 	}
-	if (sel_next && tid == 0) roles();
+	if (sel_next && tid == 0) next_roles(roles_now(a.sel), sel_next, 1, frozen);
 	if (plan) {   // the counting for the plan, by this one workgroup over all slots (whole waves: the vector holds a multiple of 64 slots)
 		for (int base = 0; base < P; base += 256) {
 			const int gs = base + tid;

@@ -590,33 +590,26 @@ __global__ __launch_bounds__(64) void k_wait_landing(const MigPlan pl, int n, co
 }
 
 // End of a sharded step, one workgroup per local particle; what it does is read from the device plan, not decided by the
-// host (rotate_roles in phd_resample.h has the rules of the single-handle step, which are these):
-//   dropped step (a flag was raised): the roles stay as they were, nothing is touched
-//   not resampled: (IN, OUT, TMP, INMIX) = (O, I, T, O), slots identity
+// host. The roles are those of the single-handle step (next_roles / keep_roles, phd_kernels.h):
+//   dropped step (the plan's status is not MIG_OK): keep_roles
+//   not resampled: slots identity
 //   resampled: as in the single-handle step no local mixture is copied — particle i whose source is a local particle reads
 //     that particle's slot of the OUT bank from now on; a particle that arrives from another rank (record j of the receive
 //     buffer) is unpacked into a slot of the OUT bank that no local particle uses as a source (fslot[j]) and read from
 //     there. Block b unpacks record b (if there is one) and sets up particle b: small arrays into TMP, slot into inslot.
-//     (IN, OUT, TMP, INMIX) = (T, I, O, O)
-//   frozen: roles and slots stay (benchmark steady state); RES / RESMIX / slots say where the result is
+//   frozen: the slots of the result go to `slots` only
 //   (with landing flags, k_wait_landing in front of this launch has seen the records of the receive buffer arrive)
 __global__ __launch_bounds__(256) void k_finish_sharded(const StepBufs a, const MigPlan pl, int n, const double* recvbuf, double weight,
                                                         int* sel_next, int frozen, int* inslot, int* slots)
 {
 	const int i = blockIdx.x, tid = threadIdx.x;
 	const int nrecv = pl.counts[mig_word(n, MC_NRECV)], status = pl.counts[mig_word(n, MC_STATUS)], resampled = pl.counts[mig_word(n, MC_RESAMPLED)];
-	const int I = a.sel[SEL_IN], O = a.sel[SEL_OUT], T = a.sel[SEL_TMP], X = a.sel[SEL_INMIX];
+	const BankRoles now = roles_now(a.sel);   // (requested with the plan's words above)
 	if (status != MIG_OK) {
-		if (i == 0 && tid < SEL_STRIDE) sel_next[tid] = a.sel[tid];
+		if (i == 0) keep_roles(a.sel, sel_next, tid);
 		return;
 	}
-	if (i == 0 && tid == 0) {
-		if (frozen)         { sel_next[SEL_IN] = I; sel_next[SEL_OUT] = O; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = X; }
-		else if (resampled) { sel_next[SEL_IN] = T; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = O; sel_next[SEL_INMIX] = O; }
-		else                { sel_next[SEL_IN] = O; sel_next[SEL_OUT] = I; sel_next[SEL_TMP] = T; sel_next[SEL_INMIX] = O; }
-		sel_next[SEL_RES]    = resampled ? T : O;
-		sel_next[SEL_RESMIX] = O;
-	}
+	if (i == 0 && tid == 0) next_roles(now, sel_next, resampled, frozen);
 	if (!resampled) {
 		if (tid == 0) {
 			slots[i] = i;

@@ -1,7 +1,5 @@
 """GPU parity cases added in round 2 (through the C-ABI, against the CPU oracle):
   * BASELINE config A (256 x 128 x 32) at its stated size, the whole step for every particle;
-  * ResampleParticles on weight vectors of 16 384 - 32 768 entries (config C8's global vector; both the LDS-staged and
-    the global-memory branch of k_normalise_resample, and the sizes around the switch);
   * the setters right behind an asynchronous step (the bank roles rotate on the device);
   * a failed step (emit capacity) leaves the state as it was;
   * means and covariances of CorrectConditional bit for bit as the oracle's (the reference's arithmetic is compiled
@@ -87,25 +85,6 @@ def test_config_A_full_size_step(nav_mod):
         olm, _ = orc.best_map_estimate(st.map(best))
         d, card = orc.ospa(glm, olm)
         assert card == 0 and d < 1e-4
-    nav.close()
-
-
-@pytest.mark.parametrize("P", [16384, 18300, 18400, 18432, 20000, 32768])
-def test_resample_large_vectors(nav_mod, P):
-    """ResampleParticles / ParticleDepleted on the global weight vector of a sharded run (C8: 16 384) and beyond, bit-exact
-    against the sequential recurrence: the LDS-staged branch (up to ~18 350 weights beside the kernel's static arrays),
-    the sizes around the switch, and the global-memory branch."""
-    p = prm3d_defaults(max_particles=4, max_components=600, max_measurements=8)
-    nav = nav_mod.PHDNavigator(p, particlecount=4)
-    rng = np.random.default_rng(P)
-    for power, u in ((8, 0.5), (1, 0.25), (30, 0.999999), (2, 1e-12)):
-        w = rng.random(P) ** power
-        w /= w.sum()
-        src, best = nav.ResampleParticles(w, u)
-        osrc, obest = orc.resample(w, u)
-        assert np.array_equal(src, osrc), "P=%d power=%d u=%g: %d sources differ" % (P, power, u, np.count_nonzero(src != osrc))
-        assert best == obest
-        assert nav.ParticleDepleted(w) == orc.particle_depleted(p, w)
     nav.close()
 
 
