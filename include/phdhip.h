@@ -623,6 +623,14 @@ int phd_test_ascent_control(phd_navigator* nav, const double* pose6, const doubl
 int phd_test_pairing(phd_navigator* nav, const double* matrix, int n, int mode, int modelsize, int maxcount,
                      int32_t* assignments, double* values, int* count);
 
+/* Test surface for the device arithmetic primitives (exp_neg / exp_pair and their table, gauss_record / gauss_logw, the
+ * double-double helpers of the resampling, small_div, the weight bins, the fixed-order reductions and scans, the 3 x 3
+ * algebra): k_test_primitive calls the function `op` names on every record of `in` and writes the records of `out`. Both
+ * are raw bytes in the layout monorfs_amd/csrc/phd_primitives_test.h documents per op, so that bit patterns pass
+ * unchanged. PHD_ERR_BAD_ARGUMENT for an unknown op or sizes that do not match its layout. A multi-device handle runs
+ * it on its first shard. tests/test_gpu_primitives.py holds each primitive to a multi-precision reference through it.   */
+int phd_test_primitive(phd_navigator* nav, int op, const void* in, int64_t in_bytes, void* out, int64_t out_bytes);
+
 /* Per-kernel device time in milliseconds, from HIP events recorded around every launch on the
  * handle's stream: the mean over the launches since the last phd_timing_reset; names[i] -> ms[i];
  * returns the number of entries. phd_timing_reset(nav, 0) switches the events off; (nav, n) times every n-th

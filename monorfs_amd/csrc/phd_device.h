@@ -308,10 +308,11 @@ __device__ __forceinline__ double quad_gen(const double A[9], double d0, double 
 }
 
 // exp(x) for the Gaussian exponents of the pair loops (x <= 0 in exact arithmetic):
-//   x = (32 k + j) ln2/32 + r,  exp(x) = 2^k * 2^(j/32) * e^r,  |r| <= ln2/64
-// with 2^(j/32) from a 32-entry table in LDS and e^r by a degree-6 Taylor polynomial: a dependent chain of
-// 6 fused multiply-adds instead of the ~14 of a table-free evaluation. Measured against libm on [-700, 0]:
-// <= 2 ulp (3.9e-16). A NaN stays a NaN, anything below -800 gives 0 like exp does.
+//   x = (256 k + j) ln2/256 + r,  exp(x) = 2^k * 2^(j/256) * e^r,  |r| <= ln2/512
+// with 2^(j/256) from a 256-entry table in LDS (exp_tab_init, every entry within 1 ulp) and e^r by a short Taylor polynomial:
+// degree 4 in exp_neg, degree 3 in exp_pair — a dependent chain of 4 / 3 fused multiply-adds instead of the ~14 of a table-free
+// evaluation. Both, the table and the composition with gauss_logw are held to a multi-precision reference with derived bounds
+// by tests/test_gpu_primitives.py (bounds and inputs: tests/primitive_cases.py; DESIGN §2, "Device primitives").
 #define EXPTAB_N 256
 __device__ __forceinline__ void exp_tab_init(double* T, int tid)
 {
@@ -319,7 +320,9 @@ __device__ __forceinline__ void exp_tab_init(double* T, int tid)
 }
 
 // exp(x) for x in (-inf, 700]: x = (256 n' + j) ln2 / 256 + r, exp(x) = 2^n' * T[j] * p(r) with |r| <= ln2 / 512 and
-// p the degree-4 Taylor polynomial (truncation 4e-17 relative). Below -800 the result is 0; a NaN stays a NaN.
+// p the degree-4 Taylor polynomial (truncation 4e-17 relative). Below -800 the result is 0; a NaN stays a NaN. Bound for a
+// normal result: 4.85e-16 relative (table 2^-52, last fma 2^-53, t * p 2^-53, truncation, reduction); measured on an MI355X
+// against mpmath over 1.05e5 points of [-800, 700]: 3.23e-16, at x = -395.669 (tests/test_gpu_primitives.py).
 __device__ __forceinline__ double exp_neg(double x, const double* __restrict__ T)
 {
 	x = (x < -800.0) ? -800.0 : x;
@@ -337,7 +340,8 @@ __device__ __forceinline__ double exp_neg(double x, const double* __restrict__ T
 
 // The same for the dense pair loops (k_sweep's weight sums, k_alpha_density), four instructions leaner at the front: the
 // argument is clamped by one v_max_f64 and rounded by adding 1.5 * 2^52, which leaves the integer in the low word of the
-// sum (no v_rndne / v_cvt). Same table, a polynomial one degree shorter (relative 1.4e-13, below); a NaN
+// sum (no v_rndne / v_cvt). Same table, a polynomial one degree shorter (bound 1.40e-13 + 8.1e-17 |x| + 4.9e-16 relative, below;
+// measured on an MI355X against mpmath: 1.63e-13 at x = -689.77, 0.998 of the bound at the worst point); a NaN
 // argument counts as exp(-800) = 0 here (v_max_f64 returns the other operand), where exp_neg keeps it a NaN.
 // keep = false: the result is 0 (the exponent handed to v_ldexp_f64 is replaced: one 32-bit select instead of two on the value)
 __device__ __forceinline__ double exp_pair(double x, const double* __restrict__ T, bool keep = true)

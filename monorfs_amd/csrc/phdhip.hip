@@ -12,6 +12,7 @@
 #include "phd_ascent.h"
 #include "phd_ascent_multi.h"
 #include "phd_hold.h"
+#include "phd_primitives_test.h"   // (last of the headers: k_test_primitive is the last kernel that is no template; the instantiations follow it)
 #include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
 
 #include <algorithm>
@@ -1664,6 +1665,47 @@ int phd_test_pairing(phd_navigator* nav, const double* matrix, int n, int mode, 
 	if (e == hipSuccess && k > 0) e = hipMemcpy(values, dv, (size_t) k * 8, hipMemcpyDeviceToHost);
 	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_pairing: ") + hipGetErrorString(e));
 	*count = m;
+	return PHD_OK;
+}
+
+int phd_test_primitive(phd_navigator* nav, int op, const void* in, int64_t in_bytes, void* out, int64_t out_bytes)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);
+	PrimLayout l;
+	if (!primitive_layout(op, l)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_test_primitive: unknown op");
+	int64_t n = l.fixed_n;
+	bool fits = in_bytes >= l.head && out && (in || in_bytes == 0);
+	if (fits && !l.fixed_n) {
+		n = (in_bytes - l.head) / l.in_rec;
+		fits = n >= 1 && n <= PT_MAX_RECORDS && (in_bytes - l.head) == n * l.in_rec && (!l.whole || n % l.block == 0) && (op != PT_SMALL_DIV || n <= 1024);
+	} else if (fits) {
+		fits = in_bytes == l.head;
+	}
+	if (!fits || out_bytes != n * l.out_rec) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_test_primitive: the sizes do not match the op's record layout (phd_primitives_test.h)");
+	}
+	if (op == PT_SMALL_DIV) {
+		for (int64_t t = 0; t < n; t++) {
+			const int32_t d = ((const int32_t*) in)[t];
+			if (d < 1 || d >= PT_SMALL_DIV_RANGE) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_test_primitive: small_div takes 1 <= d < 2^24");
+		}
+	}
+	enter(nav);
+	HC(hipStreamSynchronize(nav->stream));
+	DevBuf<char> din, dout;
+	HC(din.alloc((size_t) std::max<int64_t>(in_bytes, 8)));
+	HC(dout.alloc((size_t) out_bytes));
+	hipError_t e = in_bytes ? hipMemcpy(din, in, (size_t) in_bytes, hipMemcpyHostToDevice) : hipSuccess;
+	if (e == hipSuccess) e = hipMemsetAsync(dout, 0, (size_t) out_bytes, nav->stream);   // (on the kernel's stream: it must land before the kernel writes)
+	if (e == hipSuccess) {
+		const dim3 grid = (op == PT_SMALL_DIV) ? dim3(PT_SMALL_DIV_RANGE / (256 * PT_SMALL_DIV_PER_THREAD), (unsigned) n) : dim3((unsigned) ((n + l.block - 1) / l.block));
+		hipLaunchKernelGGL(k_test_primitive, grid, dim3(l.block), PT_LDS_DOUBLES * sizeof(double), nav->stream, op, (const char*) din, (char*) dout, (int) n);
+		e = hipGetLastError();
+		if (e == hipSuccess) e = hipStreamSynchronize(nav->stream);
+	}
+	if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t) out_bytes, hipMemcpyDeviceToHost);
+	if (e != hipSuccess) return nav->fail(PHD_ERR_DEVICE, std::string("phd_test_primitive: ") + hipGetErrorString(e));
 	return PHD_OK;
 }
 

@@ -628,6 +628,15 @@ class PHDNavigator:
         k = min(cnt.value, maxcount)
         return asg[:k].tolist(), val[:k].copy()
 
+    def test_primitive(self, op, in_array, out_dtype, out_count):
+        """one device arithmetic primitive on raw records (phd_test_primitive; ops and record layouts:
+        monorfs_amd/csrc/phd_primitives_test.h): the bytes of `in_array` in, `out_count` items of `out_dtype` back"""
+        a = np.ascontiguousarray(in_array)
+        out = np.zeros(int(out_count), out_dtype)
+        self._check(self._lib.phd_test_primitive(self._h, int(op), a.ctypes.data_as(C.c_void_p) if a.nbytes else None, a.nbytes,
+                                                 out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     # ------------------------------------------------------------------ benchmark surface
     def set_measurements(self, measurements):
         z = np.ascontiguousarray(measurements, np.float64).reshape(-1, 3)
