@@ -51,6 +51,7 @@ public class PhdHipLib
 	[DllImport(Lib)] public extern static int    phd_quasi_ascent(HandleRef nav, IntPtr initial6, int nestimates, IntPtr linearpoint7, IntPtr landmarks3, int nlandmarks, IntPtr z3, int nmeasurements, int averagemode, int maxiterations, int rounditerations, IntPtr poses6, IntPtr values, IntPtr iterations, IntPtr hessians36);
 	[DllImport(Lib)] public extern static int    phd_quasi_ascent_multi(HandleRef nav, int nproblems, IntPtr landmarkoffsets, IntPtr landmarks3, IntPtr measurementoffsets, IntPtr z3, IntPtr linearpoints7, IntPtr initial6, IntPtr problem, int nestimates, int averagemode, int maxiterations, int rounditerations, IntPtr poses6, IntPtr values, IntPtr iterations, IntPtr hessians36);
 	[DllImport(Lib)] public extern static int    phd_quasi_set_loglik_multi(HandleRef nav, int nproblems, IntPtr landmarkoffsets, IntPtr landmarks3, IntPtr measurementoffsets, IntPtr z3, IntPtr poses7, IntPtr problem, int nposes, int averagemode, IntPtr values, IntPtr gradients6);
+	[DllImport(Lib)] public extern static int    phd_quasi_guesses_multi(HandleRef nav, int nproblems, IntPtr landmarkoffsets, IntPtr landmarks3, IntPtr measurementoffsets, IntPtr z3, IntPtr linearpoints7, IntPtr pose0s6, IntPtr farpose7, double radius, int capacity, IntPtr guessoffsets, IntPtr pairs2, IntPtr guesses6, IntPtr poses7, IntPtr values, IntPtr emptyspace);
 	[DllImport(Lib)] public extern static int    phd_set_depth_map(HandleRef nav, IntPtr depth, int width, int height);
 	[DllImport(Lib)] public extern static int    phd_slam_update(HandleRef nav, IntPtr z3, int nmeasurements, [MarshalAs(UnmanagedType.U1)] bool onlymapping, double uresample);
 	[DllImport(Lib)] public extern static int    phd_set_measurements(HandleRef nav, IntPtr z3, int nmeasurements);
@@ -445,6 +446,62 @@ public unsafe class HipPHDNavigatorCore<MeasurerT> : Navigator<MeasurerT, Pose3D
 		double[][] poses = new double[n][];
 		for (int i = 0; i < n; i++) { poses[i] = new double[6]; Array.Copy(result, 6 * i, poses[i], 0, 6); }
 		return poses;
+	}
+
+	/// <summary>The guess loop of GuidedFitMixture (LoopyPHDNavigator.cs:789-797) and the first evaluation of every guess (:808-823)
+	/// for many frames in one call (phd_quasi_guesses_multi). Frame q has the map estimate maps[q], the measurements
+	/// measurements[q], the linearisation pose linearpoints[q] and the initial linear pose pose0s[q]. guesses[q] is the list the
+	/// reference builds: pose0s[q], then, landmark by landmark and measurement by measurement, FitToMeasurement's pose where it lies
+	/// within `radius` of the initial pose, as a linear pose around linearpoints[q]; values[q][e] is QuasiSetLogLikelihood at
+	/// linearpoints[q].Add(guesses[q][e]) and emptyspace[q] its value at the pose far from everything. The frames of one call lie
+	/// in one measurement-block class, as for DeviceLogLikeGradientAscentMulti. A call whose arrays were too small is repeated
+	/// once with the total the library reports.</summary>
+	public double[][][] DeviceGuidedGuesses(double[][] pose0s, List<List<PixelRangeMeasurement>> measurements, List<IMap> maps, Pose3D[] linearpoints,
+	                                        out double[][] values, out double[] emptyspace, double radius = 0.5)
+	{
+		const int StatusCapacity = 2;                                     // PHD_ERR_CAPACITY
+		int np = maps.Count;
+		int[] lmoff = new int[np + 1], zoff = new int[np + 1], goff = new int[np + 1];
+		for (int q = 0; q < np; q++) { lmoff[q + 1] = lmoff[q] + maps[q].Count; zoff[q + 1] = zoff[q] + measurements[q].Count; }
+		double[] z = new double[3 * zoff[np] + 3], lm = new double[3 * lmoff[np] + 3], p6 = new double[6 * np], lin = new double[7 * np];
+		for (int q = 0; q < np; q++) {
+			for (int i = 0; i < measurements[q].Count; i++) { measurements[q][i].ToLinear().CopyTo(z, 3 * (zoff[q] + i)); }
+			int j = lmoff[q];
+			foreach (Gaussian landmark in maps[q]) { landmark.Mean.CopyTo(lm, 3 * j++); }
+			linearpoints[q].State.CopyTo(lin, 7 * q);
+			pose0s[q].CopyTo(p6, 6 * q);
+		}
+		double[] far = Pose3D.Identity.Add(new double[] {1e5, 1e5, 1e5, 1e5, 1e5, 1e5}).State;   // :808
+		emptyspace = new double[np];
+		int capacity = np + 64 * np;
+		int[] pairs = null;
+		double[] g6 = null, p7 = null, v = null;
+		for (int attempt = 0; attempt < 2; attempt++) {
+			pairs = new int[2 * capacity]; g6 = new double[6 * capacity]; p7 = new double[7 * capacity]; v = new double[capacity];
+			int status;
+			fixed (double* pz = z) fixed (double* pl = lm) fixed (double* pp = p6) fixed (double* plin = lin) fixed (double* pf = far) fixed (double* pg = g6)
+			fixed (double* pq = p7) fixed (double* pv = v) fixed (double* pe = emptyspace) fixed (int* plo = lmoff) fixed (int* pzo = zoff) fixed (int* pgo = goff)
+			fixed (int* ppr = pairs) {
+				status = PhdHipLib.phd_quasi_guesses_multi(nav, np, (IntPtr) plo, (IntPtr) pl, (IntPtr) pzo, (IntPtr) pz, (IntPtr) plin, (IntPtr) pp, (IntPtr) pf, radius,
+				                                           capacity, (IntPtr) pgo, (IntPtr) ppr, (IntPtr) pg, (IntPtr) pq, (IntPtr) pv, (IntPtr) pe);
+			}
+			if (status == StatusCapacity && attempt == 0) { capacity = goff[np]; continue; }   // (guess_offsets is set: the total)
+			Check(status);
+			break;
+		}
+		double[][][] guesses = new double[np][][];
+		values = new double[np][];
+		for (int q = 0; q < np; q++) {
+			int count = goff[q + 1] - goff[q];
+			guesses[q] = new double[count][];
+			values[q] = new double[count];
+			for (int e = 0; e < count; e++) {
+				guesses[q][e] = new double[6];
+				Array.Copy(g6, 6 * (goff[q] + e), guesses[q][e], 0, 6);
+				values[q][e] = v[goff[q] + e];
+			}
+		}
+		return guesses;
 	}
 
 	Map MapOfParticle(int particle)

@@ -608,6 +608,36 @@ int phd_quasi_set_loglik_multi(phd_navigator* nav, int nproblems,
                                const double* poses7, const int32_t* problem, int nposes,
                                int average_mode, double* out, double* gradients6 /* or NULL */);
 
+/* The starting guesses of the pose searches of many frames (monorfs_amd/csrc/phd_guesses.h): the guess loop of
+ * LoopyPHDNavigator.GuidedFitMixture (:789-797) for every problem of a call, and the first evaluation of every guess
+ * (:808-823). Problems as for phd_quasi_ascent_multi — the same offsets arrays, limits and one-block-class rule —, each with
+ * its linearisation pose linearpoints7[q] and its initial linear pose pose0s6[q]; initpose = linearpoint.Add(pose0).
+ * The guesses of problem q stand at guess_offsets[q] .. guess_offsets[q + 1] in the reference's order: pose0s6[q] itself
+ * (pairs2 = -1, -1), then, landmark-major and measurement-minor, every (landmark, measurement) pair whose fitted pose g
+ * (PRM3DMeasurer.FitToMeasurement at initpose, PRM3DMeasurer.cs:221-243) has |g.Subtract(initpose)|^2 < radius^2 (0.5 in
+ * the reference, :793), stored as g.Subtract(linearpoint). A pair whose fit is not finite (a landmark at the pose's
+ * location, a landmark direction exactly opposite the measurement's) makes no guess: the comparison is false on NaN.
+ * pairs2[e] = (landmark, measurement), problem-local. poses7[e] = linearpoint.Add(guesses6[e]), the pose a search forms from
+ * the same guess; values[e] is bit for bit what phd_quasi_set_loglik_multi returns for poses7[e], emptyspace[q] what it
+ * returns for farpose7 (the pose far from everything, :808) against problem q. The evaluations run inside the call, at most
+ * max_particles poses a launch.
+ * capacity: the guesses pairs2 / guesses6 / poses7 / values hold. More guesses than that: PHD_ERR_CAPACITY with guess_offsets
+ * fully set (guess_offsets[nproblems] is the capacity a retry needs) and every other output untouched. capacity < nproblems,
+ * a radius that is not finite and > 0, a NULL handle or array, bad offsets, a limit, mixed classes or non-finite input:
+ * PHD_ERR_BAD_ARGUMENT before anything is enqueued, the outputs untouched. PHD_FLAG_BIG_CLUSTER in any evaluation:
+ * PHD_ERR_ASSOCIATION. Synchronous; buffers of its own per handle: the particle state, the logs and the other calls' flag
+ * words and slab counters are not touched; a multi-device handle uses its first shard.                                  */
+int phd_quasi_guesses_multi(phd_navigator* nav, int nproblems,
+                            const int32_t* landmark_offsets, const double* landmarks3,
+                            const int32_t* measurement_offsets, const double* z3,
+                            const double* linearpoints7 /* [nproblems][7] */,
+                            const double* pose0s6 /* [nproblems][6] */,
+                            const double* farpose7 /* [7] */, double radius, int capacity,
+                            int32_t* guess_offsets /* [nproblems + 1] */,
+                            int32_t* pairs2 /* [capacity][2] */,
+                            double* guesses6 /* [capacity][6] */, double* poses7 /* [capacity][7] */,
+                            double* values /* [capacity] */, double* emptyspace /* [nproblems] */);
+
 /* Test surface for the control kernels of phd_quasi_ascent: k_ascent_candidates, then k_ascent_select on the caller's
  * values16[nestimates][16], no evaluation in between, every estimate active. Returns cand6[n][16][6], cand7[n][16][7], the
  * index of the candidate the line search ended on, the new pose6 / loglike, nextpose7 and the active word.              */

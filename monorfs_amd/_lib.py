@@ -9,7 +9,7 @@ from .abi import PhdParams
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("PHDHIP_SO") or os.path.join(CSRC, "libphdhip.so")   # (PHDHIP_SO: another build of the same library, for A/B timing)
-SOURCES = ["phdhip.hip", "phd_multi.inc", "phd_kernels.h", "phd_correct.h", "phd_sweep.h", "phd_prune.h", "phd_alpha.h", "phd_resample.h", "phd_shard.h", "phd_history.h", "phd_maplog.h", "phd_maperror.h", "phd_poseerror.h", "phd_ascent.h", "phd_ascent_multi.h", "phd_hold.h", "phd_primitives_test.h", "phd_device.h"]
+SOURCES = ["phdhip.hip", "phd_multi.inc", "phd_kernels.h", "phd_correct.h", "phd_sweep.h", "phd_prune.h", "phd_alpha.h", "phd_resample.h", "phd_shard.h", "phd_history.h", "phd_maplog.h", "phd_maperror.h", "phd_poseerror.h", "phd_ascent.h", "phd_ascent_multi.h", "phd_guesses.h", "phd_hold.h", "phd_primitives_test.h", "phd_device.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 
 dp = C.POINTER(C.c_double)
@@ -90,6 +90,7 @@ def load():
         "phd_quasi_ascent": (C.c_int, [P, dp, C.c_int, dp, dp, C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, dp]),
         "phd_quasi_ascent_multi": (C.c_int, [P, C.c_int, ip, dp, ip, dp, dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, dp]),
         "phd_quasi_set_loglik_multi": (C.c_int, [P, C.c_int, ip, dp, ip, dp, dp, ip, C.c_int, C.c_int, dp, dp]),
+        "phd_quasi_guesses_multi": (C.c_int, [P, C.c_int, ip, dp, ip, dp, dp, dp, dp, C.c_double, C.c_int, ip, ip, dp, dp, dp, dp]),
         "phd_test_ascent_control": (C.c_int, [P, dp, dp, dp, dp, C.c_int, dp, dp, dp, ip, dp, dp, dp, ip]),
         "phd_test_pairing": (C.c_int, [P, dp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, C.POINTER(C.c_int)]),
         "phd_test_primitive": (C.c_int, [P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
@@ -160,5 +161,5 @@ EXPORTS = ["phd_api_version", "phd_default_params", "phd_create", "phd_create_mu
            "phd_migration_set_peers", "phd_migration_recv_is_finegrained", "phd_migration_push_async", "phd_migration_set_landing", "phd_stream", "phd_set_stream", "phd_timing_reset", "phd_last_timings", "phd_last_timing_counts", "phd_upload_state_soa",
            "phd_download_state_soa", "phd_set_depth_map", "phd_test_detection_probability",
            "phd_history_enable", "phd_history_append", "phd_trajectories",
-           "phd_trajectories_at", "phd_map_history_enable", "phd_map_history_append", "phd_map_history", "phd_map_error", "phd_pose_error", "phd_quasi_ascent", "phd_test_ascent_control", "phd_step_hold_async", "phd_quasi_ascent_multi", "phd_quasi_set_loglik_multi",
+           "phd_trajectories_at", "phd_map_history_enable", "phd_map_history_append", "phd_map_history", "phd_map_error", "phd_pose_error", "phd_quasi_ascent", "phd_test_ascent_control", "phd_step_hold_async", "phd_quasi_ascent_multi", "phd_quasi_set_loglik_multi", "phd_quasi_guesses_multi",
            "phd_test_primitive"]

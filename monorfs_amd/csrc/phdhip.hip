@@ -11,6 +11,7 @@
 #include "phd_poseerror.h"
 #include "phd_ascent.h"
 #include "phd_ascent_multi.h"
+#include "phd_guesses.h"
 #include "phd_hold.h"
 #include "phd_primitives_test.h"   // (last of the headers: k_test_primitive is the last kernel that is no template; the instantiations follow it)
 #include "../host/Ospa.hpp"   // MapErrorAlignment: the alignment of phd_map_error is the host metric's, computed by the same function
@@ -148,6 +149,12 @@ struct phd_navigator {
 	DevBuf<double> d_amulti;      // phd_quasi_ascent_multi / phd_quasi_set_loglik_multi: the same for a call over many problems (multi_layout); grows to the largest call
 	PinBuf<double> h_amulti;
 	size_t amulti_cap = 0;        // doubles either holds
+	DevBuf<double> d_guess;       // phd_quasi_guesses_multi: the problems of a call, its tile words and its flag word and slab counter (guess_layout); grows to the largest call
+	PinBuf<double> h_guess;
+	size_t guess_cap = 0;
+	DevBuf<double> d_gout;        // ... and what it makes per guess (guess_out_layout), sized once the total is known
+	PinBuf<double> h_gout;
+	size_t gout_cap = 0;
 	DevBuf<double> d_gw; int gwcap = 0;              // gathered weights of all ranks (+ their status words behind them: flagslot)
 	DevBuf<double> d_stage;                          // device staging of phd_set_poses / phd_set_weights (stored into the IN bank by k_store_small)
 	// pinned host staging of the per-frame inputs (poses, weights, odometry + noise, measurements): the caller's buffers are
@@ -1587,6 +1594,157 @@ int phd_quasi_set_loglik_multi(phd_navigator* nav, int nproblems, const int32_t*
 	if (flags & PHD_FLAG_BIG_CLUSTER) {
 		return nav->fail(PHD_ERR_ASSOCIATION, "phd_quasi_set_loglik_multi: an association cluster exceeds the on-device solver");
 	}
+	return PHD_OK;
+}
+
+namespace {
+
+// phd_quasi_guesses_multi, in doubles (the int arrays two to a double). What the call is given and what the count pass leaves:
+//   lm_off[np + 1] | z_off[np + 1] | tile_first[np + 1] | landmarks[sum J][3] | z[sum M][3] | lin[np][7] | pose0[np][6] | far[7] | head[4]   <- ONE copy in
+//   | guess_offsets[np + 1] | tile_count[ntiles] | tile_scan[ntiles + 1]
+// head: the flag word and the slab counter of this call's evaluations, its own.
+struct GuessLayout { size_t lmoff, zoff, tfirst, lm, z, lin, pose0, far7, head, goff, tcount, tscan, end; };
+
+GuessLayout guess_layout(size_t np, size_t sumJ, size_t sumM, size_t ntiles)
+{
+	GuessLayout l;
+	l.lmoff = 0; l.zoff = l.lmoff + (np + 2) / 2; l.tfirst = l.zoff + (np + 2) / 2; l.lm = l.tfirst + (np + 2) / 2;
+	l.z = l.lm + sumJ * 3; l.lin = l.z + sumM * 3; l.pose0 = l.lin + np * 7; l.far7 = l.pose0 + np * 6; l.head = l.far7 + 7;
+	l.goff = l.head + 4; l.tcount = l.goff + (np + 2) / 2; l.tscan = l.tcount + (ntiles + 1) / 2; l.end = l.tscan + (ntiles + 2) / 2;
+	return l;
+}
+
+// ... and per guess, for n guesses, once the total is known: the evaluated poses are the far pose of every problem, then the guesses
+//   problem_of[np + n] | pairs[n][2] | guesses6[n][6] | poses7[np + n][7] | values[np + n]      (from pairs on: ONE copy out)
+struct GuessOutLayout { size_t problem, pairs, guesses, poses, values, end; };
+
+GuessOutLayout guess_out_layout(size_t np, size_t n)
+{
+	GuessOutLayout l;
+	l.problem = 0; l.pairs = l.problem + (np + n + 1) / 2; l.guesses = l.pairs + n; l.poses = l.guesses + n * 6;
+	l.values = l.poses + (np + n) * 7; l.end = l.values + np + n;
+	return l;
+}
+
+int guess_ensure(phd_navigator* nav, DevBuf<double>& d, PinBuf<double>& h, size_t& cap, size_t doubles)
+{
+	if (d && h && doubles <= cap) return PHD_OK;
+	HC(hipStreamSynchronize(nav->stream));
+	cap = 0;
+	HC(d.alloc(doubles));
+	HC(h.alloc(doubles, hipHostMallocDefault));
+	cap = doubles;
+	return PHD_OK;
+}
+
+}  // namespace
+
+// The guess loop of GuidedFitMixture for many problems, and the first evaluation of every guess (phd_guesses.h)
+int phd_quasi_guesses_multi(phd_navigator* nav, int nproblems, const int32_t* landmark_offsets, const double* landmarks3,
+                            const int32_t* measurement_offsets, const double* z3, const double* linearpoints7, const double* pose0s6,
+                            const double* farpose7, double radius, int capacity, int32_t* guess_offsets, int32_t* pairs2,
+                            double* guesses6, double* poses7, double* values, double* emptyspace)
+{
+	if (!nav) return PHD_ERR_BAD_ARGUMENT;
+	if (nav->multi) nav = multi_shard0(nav);   // as the other multi calls
+	const char* who = "phd_quasi_guesses_multi";
+	if (!linearpoints7 || !pose0s6 || !farpose7 || !guess_offsets || !pairs2 || !guesses6 || !poses7 || !values || !emptyspace) {
+		return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_guesses_multi: a NULL array");
+	}
+	if (!std::isfinite(radius) || !(radius > 0)) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_guesses_multi: the radius is not a positive finite number");
+	int zb = 1;
+	int rc = multi_validate(nav, who, nproblems, landmark_offsets, landmarks3, measurement_offsets, z3, landmark_offsets /* (no item names a problem) */, 0, &zb);
+	if (rc) return rc;
+	const int np = nproblems;
+	if (capacity < np) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_guesses_multi: the capacity is below one guess (pose0) per problem");
+	FINITE_OR_FAIL(nav, linearpoints7, (size_t) np * 7, "phd_quasi_guesses_multi");
+	FINITE_OR_FAIL(nav, pose0s6, (size_t) np * 6, "phd_quasi_guesses_multi");
+	FINITE_OR_FAIL(nav, farpose7, 7, "phd_quasi_guesses_multi");
+	std::vector<int32_t> tfirst((size_t) np + 1, 0);
+	long long most = (long long) np;   // guesses at most: every pair and a pose0 per problem
+	int maxt = 1;
+	for (int q = 0; q < np; q++) {
+		const long long pairs = (long long) (landmark_offsets[q + 1] - landmark_offsets[q]) * (measurement_offsets[q + 1] - measurement_offsets[q]);
+		const long long t = (pairs + PHD_GUESS_TILE - 1) / PHD_GUESS_TILE;
+		most += pairs;
+		if (most > 0x7fffffffLL || (long long) tfirst[q] + t > 0x7fffffffLL) return nav->fail(PHD_ERR_BAD_ARGUMENT, "phd_quasi_guesses_multi: more pairs than a 32-bit guess offset counts");
+		tfirst[q + 1] = tfirst[q] + (int32_t) t;
+		maxt = std::max(maxt, (int) t);
+	}
+	const int ntiles = tfirst[np];
+	enter(nav);
+	const size_t sumJ = landmark_offsets[np], sumM = measurement_offsets[np];
+	const GuessLayout l = guess_layout(np, sumJ, sumM, ntiles);
+	rc = guess_ensure(nav, nav->d_guess, nav->h_guess, nav->guess_cap, l.end);
+	if (rc) return rc;
+	double* const d = nav->d_guess;
+	double* const h = nav->h_guess;
+	std::memcpy(h + l.lmoff, landmark_offsets, (size_t) (np + 1) * 4);
+	std::memcpy(h + l.zoff, measurement_offsets, (size_t) (np + 1) * 4);
+	std::memcpy(h + l.tfirst, tfirst.data(), (size_t) (np + 1) * 4);
+	if (sumJ) std::memcpy(h + l.lm, landmarks3, sumJ * 3 * 8);
+	if (sumM) std::memcpy(h + l.z, z3, sumM * 3 * 8);
+	std::memcpy(h + l.lin, linearpoints7, (size_t) np * 7 * 8);
+	std::memcpy(h + l.pose0, pose0s6, (size_t) np * 6 * 8);
+	std::memcpy(h + l.far7, farpose7, 7 * 8);
+	std::memset(h + l.head, 0, 4 * 8);
+	hipStream_t st = nav->stream;
+	HC(hipMemcpyAsync(d, h, l.goff * 8, hipMemcpyHostToDevice, st));
+	GuessBufs g;
+	g.np = np; g.ntiles = ntiles; g.capacity = 0;
+	g.focal = nav->dp.focal; g.radius2 = radius * radius;
+	g.lm_off = (const int*) (d + l.lmoff); g.z_off = (const int*) (d + l.zoff); g.tile_first = (const int*) (d + l.tfirst);
+	g.lm = d + l.lm; g.z = d + l.z; g.lin = d + l.lin; g.pose0 = d + l.pose0; g.far7 = d + l.far7;
+	g.tile_count = (int*) (d + l.tcount); g.tile_scan = (int*) (d + l.tscan); g.goff = (int*) (d + l.goff);
+	g.problem_of = nullptr; g.poses7 = nullptr; g.pairs2 = nullptr; g.guesses6 = nullptr;
+	const dim3 grid((unsigned) np, (unsigned) maxt);
+	if (ntiles) hipLaunchKernelGGL(k_guess_count, grid, dim3(256), 0, st, g);
+	hipLaunchKernelGGL(k_guess_offsets, dim3(1), dim3(256), 0, st, g);
+	HC(hipGetLastError());
+	HC(hipMemcpyAsync(h + l.goff, d + l.goff, (size_t) (np + 1) * 4, hipMemcpyDeviceToHost, st));
+	HC(hipStreamSynchronize(st));
+	const int32_t* const hoff = (const int32_t*) (h + l.goff);
+	const long long n = hoff[np];
+	if (n < np || n > most) return nav->fail(PHD_ERR_DEVICE, "phd_quasi_guesses_multi: the device counted an impossible number of guesses");
+	std::memcpy(guess_offsets, hoff, (size_t) (np + 1) * 4);
+	if (n > capacity) {
+		return nav->fail(PHD_ERR_CAPACITY, "phd_quasi_guesses_multi: " + std::to_string(n) + " guesses, the output arrays hold " + std::to_string(capacity) + " (guess_offsets is set)");
+	}
+	const GuessOutLayout o = guess_out_layout(np, (size_t) n);
+	rc = guess_ensure(nav, nav->d_gout, nav->h_gout, nav->gout_cap, o.end);
+	if (rc) return rc;
+	double* const dg = nav->d_gout;
+	double* const hg = nav->h_gout;
+	g.capacity = (int) n;
+	g.problem_of = (int*) (dg + o.problem); g.pairs2 = (int*) (dg + o.pairs); g.guesses6 = dg + o.guesses; g.poses7 = dg + o.poses;
+	hipLaunchKernelGGL(k_guess_emit, grid, dim3(256), 0, st, g);
+	HC(hipGetLastError());
+	// the first values: the far pose of every problem and every guess, at most max_particles poses a launch, back to back
+	QuasiProblems pr;
+	pr.lm_off = g.lm_off; pr.z_off = g.z_off; pr.lm = g.lm; pr.z = g.z; pr.lin = g.lin;
+	int* const flags = (int*) (d + l.head);
+	unsigned long long* const slab = (unsigned long long*) (d + l.head + 1);
+	const long long all = (long long) np + n;
+	for (long long s = 0; s < all; s += nav->Pcap) {
+		const int count = (int) std::min<long long>(nav->Pcap, all - s);
+		if (s) HC(hipMemsetAsync(slab, 0, 8, st));   // every launch finds the slab counter at zero, as a batch call's does
+		pr.problem = g.problem_of + s;
+		rc = multi_eval(nav, pr, zb, flags, slab, 0, g.poses7 + s * 7, count, dg + o.values + s, nullptr, nullptr, 1);
+		if (rc) return rc;
+	}
+	HC(hipMemcpyAsync(hg + o.pairs, dg + o.pairs, (o.end - o.pairs) * 8, hipMemcpyDeviceToHost, st));
+	HC(hipMemcpyAsync(h + l.head, d + l.head, 8, hipMemcpyDeviceToHost, st));
+	HC(hipStreamSynchronize(st));
+	int fl = 0;
+	std::memcpy(&fl, h + l.head, 4);
+	if (fl & PHD_FLAG_BIG_CLUSTER) {
+		return nav->fail(PHD_ERR_ASSOCIATION, "phd_quasi_guesses_multi: an association cluster exceeds the on-device solver");
+	}
+	std::memcpy(pairs2, hg + o.pairs, (size_t) n * 8);
+	std::memcpy(guesses6, hg + o.guesses, (size_t) n * 6 * 8);
+	std::memcpy(poses7, hg + o.poses + (size_t) np * 7, (size_t) n * 7 * 8);
+	std::memcpy(values, hg + o.values + np, (size_t) n * 8);
+	std::memcpy(emptyspace, hg + o.values, (size_t) np * 8);
 	return PHD_OK;
 }
 

@@ -500,54 +500,109 @@ inline std::vector<PoseComponent> GuidedFitMixture(PHDNavigator& nav, double vis
 	return detail::MixtureOf(poses, values, [&]() { return LogLikeFitCovariance(nav, pose0, measurements, jmap, linearpoint, averagemode); });
 }
 
-// GuidedFitMixture(..., resident = true) for many frames at once (≙ the Parallel.For of UpdateMessagesFromMap, :525-551): frame i
-// has pose0s[i], measurementsets[i], maps[i] and linearpoints[i]; returns the mixtures, emptyspaces[i] the value far from
-// everything. The guesses of every frame are made on the host as there; then THREE device calls serve all frames
-// (PHDNavigator::QuasiSetLogLikelihoodMulti, QuasiAscentMulti, QuasiSetLogLikelihoodGradientMulti): the far pose and the guesses
-// of every frame, the climb of every surviving guess, the 12 Hessian poses at pose0 of every frame that kept a guess. The dedupe
-// and the weights stay per frame on the host. maxbatch: the handle's max_particles. monorfs_amd/loopy.py has the Python twin.
-inline std::vector<std::vector<PoseComponent>> GuidedFitMixtures(PHDNavigator& nav, double visionfocal, const std::vector<Odometry>& pose0s,
-                                                                 const std::vector<std::vector<PixelRangeMeasurement>>& measurementsets,
-                                                                 const std::vector<Map>& maps, const std::vector<Pose3D>& linearpoints, int maxbatch,
-                                                                 std::vector<double>* emptyspaces = nullptr, int averagemode = 0, int maxiterations = 0)
+// The guesses of many frames and their first values: what the two guess stages of GuidedFitMixtures hand to FitMixturesFromGuesses
+struct FrameGuesses {
+	std::vector<PHDNavigator::QuasiProblem>        Problems;   // frame i as a problem of the multi calls
+	std::vector<std::vector<Odometry>>             Guesses;    // per frame: pose0, then the pairs that pass, landmark-major
+	std::vector<std::vector<std::array<int, 2>>>   Pairs;      // ... their (landmark, measurement), (-1, -1) for pose0
+	std::vector<std::vector<double>>               Firsts;     // ... their first values
+	std::vector<double>                            EmptySpace; // per frame: the value of the pose far from everything
+};
+
+namespace detail {
+inline Pose3D FarPose() { return PoseAdd(Pose3D{0, 0, 0, 1, 0, 0, 0}, Odometry{1e5, 1e5, 1e5, 1e5, 1e5, 1e5}); }   // :808
+
+inline std::vector<PHDNavigator::QuasiProblem> ProblemsOf(const std::vector<std::vector<PixelRangeMeasurement>>& measurementsets,
+                                                          const std::vector<Map>& maps, const std::vector<Pose3D>& linearpoints)
 {
-	const size_t T = pose0s.size();
-	std::vector<PHDNavigator::QuasiProblem> problems(T);
-	std::vector<std::vector<Odometry>> guesses(T);
-	std::vector<size_t> at(T);
-	std::vector<Pose3D> first;
-	std::vector<int> which;
-	const Pose3D infpose = PoseAdd(Pose3D{0, 0, 0, 1, 0, 0, 0}, Odometry{1e5, 1e5, 1e5, 1e5, 1e5, 1e5});
-	for (size_t i = 0; i < T; i++) {
-		const Pose3D initpose = PoseAdd(linearpoints[i], pose0s[i]);
+	std::vector<PHDNavigator::QuasiProblem> problems(maps.size());
+	for (size_t i = 0; i < maps.size(); i++) {
 		problems[i].Landmarks = BestMapEstimate(maps[i]);
 		problems[i].Measurements = measurementsets[i];
 		problems[i].LinearPoint = linearpoints[i];
-		guesses[i] = {pose0s[i]};
-		for (const auto& landmark : problems[i].Landmarks) {
-			for (const auto& measurement : measurementsets[i]) {
-				const Pose3D guess = FitToMeasurement(visionfocal, initpose, measurement, landmark);
+	}
+	return problems;
+}
+}  // namespace detail
+
+// The guess stage of GuidedFitMixtures on the host (:789-823): the guess loop per frame, then the far pose and the guesses of every
+// frame in ONE device call (PHDNavigator::QuasiSetLogLikelihoodMulti). maxbatch: the handle's max_particles.
+inline FrameGuesses HostGuesses(PHDNavigator& nav, double visionfocal, const std::vector<Odometry>& pose0s,
+                                std::vector<PHDNavigator::QuasiProblem> problems, int maxbatch, double radius = 0.5)
+{
+	const size_t T = pose0s.size();
+	FrameGuesses out;
+	out.Guesses.resize(T); out.Pairs.resize(T); out.Firsts.resize(T); out.EmptySpace.assign(T, 0.0);
+	std::vector<size_t> at(T);
+	std::vector<Pose3D> first;
+	std::vector<int> which;
+	const Pose3D infpose = detail::FarPose();
+	for (size_t i = 0; i < T; i++) {
+		const Pose3D& lin = problems[i].LinearPoint;
+		const Pose3D initpose = PoseAdd(lin, pose0s[i]);
+		out.Guesses[i] = {pose0s[i]};
+		out.Pairs[i] = {{-1, -1}};
+		for (size_t j = 0; j < problems[i].Landmarks.size(); j++) {
+			for (size_t m = 0; m < problems[i].Measurements.size(); m++) {
+				const Pose3D guess = FitToMeasurement(visionfocal, initpose, problems[i].Measurements[m], problems[i].Landmarks[j]);
 				const Odometry d = PoseSubtract(guess, initpose);
 				double sq = 0;
 				for (double x : d) sq += x * x;
-				if (sq < 0.5 * 0.5) guesses[i].push_back(PoseSubtract(guess, linearpoints[i]));
+				if (sq < radius * radius) { out.Guesses[i].push_back(PoseSubtract(guess, lin)); out.Pairs[i].push_back({(int) j, (int) m}); }
 			}
 		}
 		at[i] = first.size();
 		first.push_back(infpose);
-		for (const Odometry& g : guesses[i]) first.push_back(PoseAdd(linearpoints[i], g));
-		which.insert(which.end(), 1 + guesses[i].size(), (int) i);
+		for (const Odometry& g : out.Guesses[i]) first.push_back(PoseAdd(lin, g));
+		which.insert(which.end(), 1 + out.Guesses[i].size(), (int) i);
 	}
+	if (T) {
+		const std::vector<double> v = nav.QuasiSetLogLikelihoodMulti(problems, first, which, maxbatch);
+		for (size_t i = 0; i < T; i++) {
+			out.EmptySpace[i] = v[at[i]];
+			out.Firsts[i].assign(v.begin() + at[i] + 1, v.begin() + at[i] + 1 + out.Guesses[i].size());
+		}
+	}
+	out.Problems = std::move(problems);
+	return out;
+}
+
+// ... and from the device: the guesses, their first values and the far pose's values of all frames from the ONE call
+// PHDNavigator::QuasiGuessesMulti (phd_quasi_guesses_multi). The same lists in the same order; a guess agrees with the host's to rounding.
+inline FrameGuesses DeviceGuesses(PHDNavigator& nav, const std::vector<Odometry>& pose0s, std::vector<PHDNavigator::QuasiProblem> problems, double radius = 0.5)
+{
+	const size_t T = pose0s.size();
+	FrameGuesses out;
+	out.Guesses.resize(T); out.Pairs.resize(T); out.Firsts.resize(T); out.EmptySpace.assign(T, 0.0);
+	if (T) {
+		const PHDNavigator::GuessesResult r = nav.QuasiGuessesMulti(problems, pose0s, detail::FarPose(), radius);
+		for (size_t i = 0; i < T; i++) {
+			for (int32_t e = r.Offsets[i]; e < r.Offsets[i + 1]; e++) {
+				out.Guesses[i].push_back(r.Guesses[e]);
+				out.Pairs[i].push_back({(int) r.Pairs[e][0], (int) r.Pairs[e][1]});
+				out.Firsts[i].push_back(r.Values[e]);
+			}
+			out.EmptySpace[i] = r.EmptySpace[i];
+		}
+	}
+	out.Problems = std::move(problems);
+	return out;
+}
+
+// The stage of GuidedFitMixtures behind the guesses (:821-850), for all frames: a guess worse than the far pose is dropped, the
+// others climb in ONE device call (QuasiAscentMulti), the 12 Hessian poses at pose0 of every frame that kept a guess are ONE more
+// (QuasiSetLogLikelihoodGradientMulti); the dedupe and the weights stay per frame on the host.
+inline std::vector<std::vector<PoseComponent>> FitMixturesFromGuesses(PHDNavigator& nav, const std::vector<Odometry>& pose0s, const FrameGuesses& fg, int maxbatch,
+                                                                      int averagemode = 0, int maxiterations = 0)
+{
+	const size_t T = pose0s.size();
+	const std::vector<PHDNavigator::QuasiProblem>& problems = fg.Problems;
 	std::vector<std::vector<PoseComponent>> results(T);
-	if (emptyspaces) emptyspaces->assign(T, 0.0);
-	if (T == 0) return results;
-	const std::vector<double> v = nav.QuasiSetLogLikelihoodMulti(problems, first, which, maxbatch);
 	std::vector<Odometry> climbing;
 	std::vector<int> owner;
 	for (size_t i = 0; i < T; i++) {
-		if (emptyspaces) (*emptyspaces)[i] = v[at[i]];
-		for (size_t g = 0; g < guesses[i].size(); g++) {
-			if (!(v[at[i] + 1 + g] - v[at[i]] < 0)) { climbing.push_back(guesses[i][g]); owner.push_back((int) i); }
+		for (size_t g = 0; g < fg.Guesses[i].size(); g++) {
+			if (!(fg.Firsts[i][g] - fg.EmptySpace[i] < 0)) { climbing.push_back(fg.Guesses[i][g]); owner.push_back((int) i); }
 		}
 	}
 	if (climbing.empty()) return results;
@@ -564,7 +619,7 @@ inline std::vector<std::vector<PoseComponent>> GuidedFitMixtures(PHDNavigator& n
 			for (double sign : {1.0, -1.0}) {
 				Odometry d = pose0s[i];
 				d[t] += sign * eps;
-				hposes.push_back(PoseAdd(linearpoints[i], d));
+				hposes.push_back(PoseAdd(problems[i].LinearPoint, d));
 				hwhich.push_back(i);
 			}
 		}
@@ -585,13 +640,32 @@ inline std::vector<std::vector<PoseComponent>> GuidedFitMixtures(PHDNavigator& n
 	return results;
 }
 
+// GuidedFitMixture(..., resident = true) for many frames at once (≙ the Parallel.For of UpdateMessagesFromMap, :525-551): frame i
+// has pose0s[i], measurementsets[i], maps[i] and linearpoints[i]; returns the mixtures, emptyspaces[i] the value far from
+// everything. Two stages. The guess stage makes every frame's guesses and their first values: on the host with one batch call
+// (HostGuesses), or with device_guesses as the one call PHDNavigator::QuasiGuessesMulti (DeviceGuesses) — the same lists, each
+// guess to rounding. FitMixturesFromGuesses does the rest with two more device calls. maxbatch: the handle's max_particles.
+// monorfs_amd/loopy.py has the Python twin.
+inline std::vector<std::vector<PoseComponent>> GuidedFitMixtures(PHDNavigator& nav, double visionfocal, const std::vector<Odometry>& pose0s,
+                                                                 const std::vector<std::vector<PixelRangeMeasurement>>& measurementsets,
+                                                                 const std::vector<Map>& maps, const std::vector<Pose3D>& linearpoints, int maxbatch,
+                                                                 std::vector<double>* emptyspaces = nullptr, int averagemode = 0, int maxiterations = 0,
+                                                                 bool device_guesses = false)
+{
+	std::vector<PHDNavigator::QuasiProblem> problems = detail::ProblemsOf(measurementsets, maps, linearpoints);
+	const FrameGuesses fg = device_guesses ? DeviceGuesses(nav, pose0s, std::move(problems)) : HostGuesses(nav, visionfocal, pose0s, std::move(problems), maxbatch);
+	if (emptyspaces) *emptyspaces = fg.EmptySpace;
+	return FitMixturesFromGuesses(nav, pose0s, fg, maxbatch, averagemode, maxiterations);
+}
+
 // The device part of LoopyPHDNavigator.UpdateMessagesFromMap (:511-552): LeaveOneOutMaps, then GuidedFitMixtures over the frames
 // < to that have measurements, each against the map it was left out of. A frame without measurements has an empty mixture and
-// the empty-space value 0 (:527-530). The temperature term and the fusions stay with the caller.
+// the empty-space value 0 (:527-530). The temperature term and the fusions stay with the caller. device_guesses: the guess stage
+// as one device call.
 inline std::vector<std::vector<PoseComponent>> MapMessageMixtures(PHDNavigator& nav, double visionfocal, const std::vector<std::pair<double, Pose3D>>& trajectory,
                                                                   const std::vector<std::pair<double, std::vector<PixelRangeMeasurement>>>& factors,
                                                                   const std::vector<Odometry>& pose0s, const std::vector<Pose3D>& linearpoints, int to,
-                                                                  int maxparticles, std::vector<double>* emptyspaces = nullptr, int averagemode = 0)
+                                                                  int maxparticles, std::vector<double>* emptyspaces = nullptr, int averagemode = 0, bool device_guesses = false)
 {
 	to = std::max(0, std::min((int) trajectory.size(), to));
 	std::vector<int> indices(to);
@@ -607,7 +681,7 @@ inline std::vector<std::vector<PoseComponent>> MapMessageMixtures(PHDNavigator& 
 		seen.push_back(i); p0.push_back(pose0s[i]); zs.push_back(factors[i].second); models.push_back(maps[i]); lins.push_back(linearpoints[i]);
 	}
 	std::vector<double> empties;
-	const std::vector<std::vector<PoseComponent>> fits = GuidedFitMixtures(nav, visionfocal, p0, zs, models, lins, maxparticles, &empties, averagemode);
+	const std::vector<std::vector<PoseComponent>> fits = GuidedFitMixtures(nav, visionfocal, p0, zs, models, lins, maxparticles, &empties, averagemode, 0, device_guesses);
 	std::vector<std::vector<PoseComponent>> out(to);
 	if (emptyspaces) emptyspaces->assign(to, 0.0);
 	for (size_t k = 0; k < seen.size(); k++) {

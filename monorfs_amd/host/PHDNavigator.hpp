@@ -322,6 +322,69 @@ public:
 		return quasiBatchMulti(problems, poses, problem, maxposes, averagemode, &gradients);
 	}
 
+	// The starting guesses of GuidedFitMixture (LoopyPHDNavigator.cs:789-797) for many problems and their first values
+	// (phd_quasi_guesses_multi): the guesses of problem q stand at Offsets[q] .. Offsets[q + 1], pose0s[q] first (pair -1, -1), then
+	// the (landmark, measurement) pairs whose fitted pose lies within `radius` of the initial pose, landmark-major. Poses =
+	// LinearPoint.Add(guess), Values = QuasiSetLogLikelihood there, EmptySpace[q] = the value of `farpose` against problem q.
+	struct GuessesResult {
+		std::vector<int32_t>                Offsets;      // [problems + 1]
+		std::vector<std::array<int32_t, 2>> Pairs;
+		std::vector<std::array<double, 6>>  Guesses;
+		std::vector<Pose3D>                 Poses;
+		std::vector<double>                 Values, EmptySpace;
+	};
+
+	// The problems are split by measurement-block class; a call that reports more guesses than its arrays hold is repeated once
+	// with the reported total; the results come back in the caller's order.
+	GuessesResult QuasiGuessesMulti(const std::vector<QuasiProblem>& problems, const std::vector<std::array<double, 6>>& pose0s,
+	                                const Pose3D& farpose, double radius = 0.5)
+	{
+		const size_t T = problems.size();
+		if (pose0s.size() != T) throw std::invalid_argument("one initial pose per problem");
+		std::vector<int> all(T);
+		for (size_t q = 0; q < T; q++) all[q] = (int) q;
+		struct Part { std::vector<int32_t> off; std::vector<std::array<int32_t, 2>> pairs; std::vector<std::array<double, 6>> guesses; std::vector<Pose3D> poses; std::vector<double> values; };
+		std::vector<Part> parts;
+		std::vector<std::pair<int, int>> where(T);   // problem q: (part, index within it)
+		GuessesResult out;
+		out.EmptySpace.assign(T, 0.0);
+		for (const std::vector<int>& idx : multiCalls(problems, all, (int) std::max<size_t>(T, 1))) {
+			const PackedProblems pk = packProblems(problems, all, idx, true);   // (idx is ascending: the problems in that order)
+			const size_t k = idx.size();
+			std::vector<std::array<double, 6>> start(k);
+			size_t pairs = 0;
+			for (size_t j = 0; j < k; j++) { start[j] = pose0s[idx[j]]; pairs += problems[idx[j]].Landmarks.size() * problems[idx[j]].Measurements.size(); }
+			Part p;
+			p.off.assign(k + 1, 0);
+			std::vector<double> empty(k);
+			int capacity = (int) (k + std::min(pairs, 64 * k));   // (every pair, or a first try of 64 a problem)
+			int rc = PHD_OK;
+			for (int attempt = 0; attempt < 2; attempt++) {
+				const size_t room = (size_t) std::max(capacity, 1);
+				p.pairs.assign(room, {0, 0}); p.guesses.assign(room, {}); p.poses.assign(room, Pose3D{}); p.values.assign(room, 0.0);
+				rc = phd_quasi_guesses_multi(nav_, (int) k, pk.lmoff.data(), pk.lm.empty() ? nullptr : pk.lm[0].data(), pk.zoff.data(),
+				                             pk.z.empty() ? nullptr : pk.z[0].data(), pk.lin[0].data(), start[0].data(), farpose.data(), radius, capacity,
+				                             p.off.data(), p.pairs[0].data(), p.guesses[0].data(), p.poses[0].data(), p.values.data(), empty.data());
+				if (rc != PHD_ERR_CAPACITY) break;
+				capacity = p.off[k];   // (guess_offsets is set: the total the retry needs)
+			}
+			check(rc);
+			for (size_t j = 0; j < k; j++) { where[idx[j]] = {(int) parts.size(), (int) j}; out.EmptySpace[idx[j]] = empty[j]; }
+			parts.push_back(std::move(p));
+		}
+		out.Offsets.assign(T + 1, 0);
+		for (size_t q = 0; q < T; q++) {
+			const Part& p = parts[where[q].first];
+			const int32_t a = p.off[where[q].second], b = p.off[where[q].second + 1];
+			out.Offsets[q + 1] = out.Offsets[q] + (b - a);
+			out.Pairs.insert(out.Pairs.end(), p.pairs.begin() + a, p.pairs.begin() + b);
+			out.Guesses.insert(out.Guesses.end(), p.guesses.begin() + a, p.guesses.begin() + b);
+			out.Poses.insert(out.Poses.end(), p.poses.begin() + a, p.poses.begin() + b);
+			out.Values.insert(out.Values.end(), p.values.begin() + a, p.values.begin() + b);
+		}
+		return out;
+	}
+
 	// KinectMeasurer's current depth frame (phd_set_depth_map): `depth` row-major [height][width] (the reference's
 	// float[ResX][ResY] frame transposed), used by every step until the next call; an empty vector switches it off
 	void setDepthMap(const std::vector<float>& depth, int width, int height)

@@ -302,49 +302,73 @@ def _mixture_of(poses, values, localcov):
     return components
 
 
-def GuidedFitMixtures(nav, pose0s, measurement_sets, models, linearpoints, average_mode=0, max_iterations=None):
-    """GuidedFitMixture(..., resident=True) for many frames at once (≙ the Parallel.For of UpdateMessagesFromMap, :525-551):
-    frame i has the initial linear pose pose0s[i], the measurements measurement_sets[i], the map models[i] = (w, mean, cov) and
-    the linearisation pose linearpoints[i]. Returns the list of (emptyspace, components), frame i's exactly what
-    GuidedFitMixture(nav, pose0s[i], measurement_sets[i], models[i], linearpoints[i], average_mode, True, max_iterations) gives.
+def _far_pose():
+    """the pose far from everything (:808)"""
+    return pose3d_add(np.array([0, 0, 0, 1.0, 0, 0, 0]), np.full(OdoSize, 1e5))
 
-    The guesses of every frame are made on the host as there. Then THREE device calls serve all frames (PHDNavigator's
-    QuasiSetLogLikelihoodMulti, QuasiAscentMulti, QuasiSetLogLikelihoodGradientMulti): the far pose and the guesses of every
-    frame, the climb of every surviving guess of every frame, the 12 Hessian poses at pose0 of every frame that kept a guess.
-    The dedupe and the weights stay per frame on the host. A `nav` without the multi methods takes the per-frame calls: that
-    fallback states what the three calls mean."""
-    T = len(pose0s)
-    if not hasattr(nav, "QuasiAscentMulti"):
-        resident = hasattr(nav, "QuasiAscent")   # (the oracle stub has the batch calls alone: the host drives its loop)
-        return [GuidedFitMixture(nav, pose0s[i], measurement_sets[i], models[i], linearpoints[i], average_mode, resident, max_iterations) for i in range(T)]
-    identity = np.array([0, 0, 0, 1.0, 0, 0, 0])
-    infpose = pose3d_add(identity, np.full(OdoSize, 1e5))
-    frames, problems = [], []
-    poses7, which = [], []
-    for i in range(T):
-        pose0 = np.asarray(pose0s[i], float).reshape(OdoSize)
-        lin = np.asarray(linearpoints[i], float)
-        z = np.asarray(measurement_sets[i], float).reshape(-1, 3)
+
+def _problems_of(pose0s, measurement_sets, models, linearpoints):
+    """frame i as a problem (map estimate, measurements, linearisation pose) of the multi calls, and its initial linear pose"""
+    problems = [(best_map_estimate(models[i]), np.asarray(measurement_sets[i], float).reshape(-1, 3), np.asarray(linearpoints[i], float))
+                for i in range(len(pose0s))]
+    return problems, [np.asarray(p, float).reshape(OdoSize) for p in pose0s]
+
+
+def HostGuessLists(params, problems, pose0s, radius=0.5):
+    """The guess loop of GuidedFitMixture (:789-797) per frame, on the host alone: (guesses, pairs) — frame i's guesses are pose0,
+    then every (landmark, measurement) pair whose fitted pose lies within `radius` of the initial pose, landmark-major;
+    pairs[i][e] = (landmark, measurement) of guess e, (-1, -1) for pose0."""
+    guesses, pairs = [], []
+    for (jmap, z, lin), pose0 in zip(problems, pose0s):
         initpose = pose3d_add(lin, pose0)
-        jmap = best_map_estimate(models[i])
-        guesses = [pose0]
-        for landmark in jmap:
-            for measurement in z:
-                guess = fit_to_measurement(nav.params, initpose, measurement, landmark)
+        mine, who = [pose0], [(-1, -1)]
+        for j, landmark in enumerate(jmap):
+            for m, measurement in enumerate(z):
+                guess = fit_to_measurement(params, initpose, measurement, landmark)
                 d = pose3d_subtract(guess, initpose)
-                if float(np.dot(d, d)) < 0.5 * 0.5:
-                    guesses.append(pose3d_subtract(guess, lin))
-        frames.append((pose0, lin, guesses, len(poses7)))
-        problems.append((jmap, z, lin))
-        poses7 += [infpose] + [pose3d_add(lin, g) for g in guesses]
-        which += [i] * (1 + len(guesses))
-    first = nav.QuasiSetLogLikelihoodMulti(problems, np.array(poses7).reshape(-1, 7), which) if T else np.zeros(0)
-    empties, climbing, owner = [], [], []
-    for i, (pose0, lin, guesses, at) in enumerate(frames):
-        emptyspace = first[at]
-        empties.append(emptyspace)
-        for g, v in zip(guesses, first[at + 1:at + 1 + len(guesses)]):
-            if not (v - emptyspace < 0):
+                if float(np.dot(d, d)) < radius * radius:
+                    mine.append(pose3d_subtract(guess, lin))
+                    who.append((j, m))
+        guesses.append(mine)
+        pairs.append(who)
+    return guesses, pairs
+
+
+def HostGuesses(nav, problems, pose0s, radius=0.5):
+    """The guess stage of GuidedFitMixtures on the host (:789-823): HostGuessLists, then the first values of every guess and the
+    value of the pose far from everything, those of all frames from ONE device call (QuasiSetLogLikelihoodMulti).
+    Returns (guesses, firsts, empties, pairs): lists per frame."""
+    infpose = _far_pose()
+    guesses, pairs = HostGuessLists(nav.params, problems, pose0s, radius)
+    poses7, which, at = [], [], []
+    for i, ((_, _, lin), mine) in enumerate(zip(problems, guesses)):
+        at.append(len(poses7))
+        poses7 += [infpose] + [pose3d_add(lin, g) for g in mine]
+        which += [i] * (1 + len(mine))
+    first = nav.QuasiSetLogLikelihoodMulti(problems, np.array(poses7).reshape(-1, 7), which) if problems else np.zeros(0)
+    return guesses, [first[a + 1:a + 1 + len(g)] for a, g in zip(at, guesses)], [first[a] for a in at], pairs
+
+
+def DeviceGuesses(nav, problems, pose0s, radius=0.5):
+    """HostGuesses from the device: the guesses, their first values and the far pose's values of all frames from the ONE call
+    nav.QuasiGuessesMulti (phd_quasi_guesses_multi). The same lists in the same order; a guess agrees with the host's to rounding."""
+    if not problems:
+        return [], [], [], []
+    off, pairs, g6, _, values, empties = nav.QuasiGuessesMulti(problems, pose0s, radius)
+    cut = lambda a: [a[off[i]:off[i + 1]] for i in range(len(problems))]
+    return [list(g) for g in cut(g6)], cut(values), list(empties), [[tuple(int(v) for v in p) for p in f] for f in cut(pairs)]
+
+
+def FitMixturesFromGuesses(nav, problems, pose0s, guesses, firsts, empties, average_mode=0, max_iterations=None):
+    """The stage of GuidedFitMixtures behind the guesses (:821-850), for all frames: a guess worse than the far pose is dropped,
+    the others climb in ONE device call (QuasiAscentMulti), the 12 Hessian poses at pose0 of every frame that kept a guess are
+    ONE more (QuasiSetLogLikelihoodGradientMulti); the dedupe and the weights stay per frame on the host. guesses[i], firsts[i],
+    empties[i]: frame i's guess list, the first values of its guesses, the far pose's value (HostGuesses / DeviceGuesses)."""
+    T = len(problems)
+    climbing, owner = [], []
+    for i in range(T):
+        for g, v in zip(guesses[i], firsts[i]):
+            if not (v - empties[i] < 0):
                 climbing.append(g)
                 owner.append(i)
     results = [(empties[i], []) for i in range(T)]
@@ -358,7 +382,7 @@ def GuidedFitMixtures(nav, pose0s, measurement_sets, models, linearpoints, avera
     eps = 1e-5
     hposes, hwhich = [], []
     for i in kept:   # the 12 poses of LogLikeFitCovariance at pose0 (which the reference never updates, :800, :839)
-        pose0, lin = frames[i][0], frames[i][1]
+        pose0, lin = pose0s[i], problems[i][2]
         for t in range(OdoSize):
             for sign in (1.0, -1.0):
                 d = pose0.copy()
@@ -375,20 +399,55 @@ def GuidedFitMixtures(nav, pose0s, measurement_sets, models, linearpoints, avera
     return results
 
 
-def MapMessageMixtures(nav, trajectory, factors, pose0s, linearpoints, to=None, average_mode=0):
-    """The device part of LoopyPHDNavigator.UpdateMessagesFromMap (:511-552): LeaveOneOutMaps, then GuidedFitMixtures over the
-    frames < to that have measurements against the map each of them was left out of. Returns one (emptyspace, components) per
-    frame; a frame without measurements gives (0.0, []) (:527-530). The temperature term and the fusions stay with the caller.
-    pose0s[i] / linearpoints[i]: the initial linear pose and the linearisation pose of frame i."""
+def GuidedFitMixturesRouted(nav, pose0s, measurement_sets, models, linearpoints, average_mode=0, max_iterations=None, device_guesses=False):
+    """GuidedFitMixture(..., resident=True) for many frames at once (≙ the Parallel.For of UpdateMessagesFromMap, :525-551):
+    frame i has the initial linear pose pose0s[i], the measurements measurement_sets[i], the map models[i] = (w, mean, cov) and
+    the linearisation pose linearpoints[i]. Returns the list of (emptyspace, components).
+
+    Two stages. The guess stage makes every frame's guesses and their first values: on the host with one batch call
+    (HostGuesses; frame i's result is then exactly GuidedFitMixture's with resident=True), or with device_guesses=True as the
+    one call nav.QuasiGuessesMulti (DeviceGuesses) — the same lists, each guess to rounding. FitMixturesFromGuesses does the
+    rest with two more device calls. A `nav` without the multi methods takes the per-frame calls: that fallback states what the
+    calls mean."""
+    T = len(pose0s)
+    if not hasattr(nav, "QuasiAscentMulti"):
+        if device_guesses:
+            raise ValueError("device_guesses=True needs a navigator with QuasiGuessesMulti")
+        resident = hasattr(nav, "QuasiAscent")   # (the oracle stub has the batch calls alone: the host drives its loop)
+        return [GuidedFitMixture(nav, pose0s[i], measurement_sets[i], models[i], linearpoints[i], average_mode, resident, max_iterations) for i in range(T)]
+    problems, starts = _problems_of(pose0s, measurement_sets, models, linearpoints)
+    guesses, firsts, empties, _ = (DeviceGuesses if device_guesses else HostGuesses)(nav, problems, starts)
+    return FitMixturesFromGuesses(nav, problems, starts, guesses, firsts, empties, average_mode, max_iterations)
+
+
+def GuidedFitMixtures(nav, pose0s, measurement_sets, models, linearpoints, average_mode=0, max_iterations=None):
+    """GuidedFitMixturesRouted with the guesses of every frame made on the host: frame i's result is exactly what
+    GuidedFitMixture(nav, pose0s[i], measurement_sets[i], models[i], linearpoints[i], average_mode, True, max_iterations) gives.
+    THREE device calls serve all frames (PHDNavigator's QuasiSetLogLikelihoodMulti, QuasiAscentMulti,
+    QuasiSetLogLikelihoodGradientMulti)."""
+    return GuidedFitMixturesRouted(nav, pose0s, measurement_sets, models, linearpoints, average_mode, max_iterations, False)
+
+
+def MapMessageMixturesRouted(nav, trajectory, factors, pose0s, linearpoints, to=None, average_mode=0, device_guesses=False):
+    """The device part of LoopyPHDNavigator.UpdateMessagesFromMap (:511-552): LeaveOneOutMaps, then GuidedFitMixturesRouted over
+    the frames < to that have measurements against the map each of them was left out of. Returns one (emptyspace, components)
+    per frame; a frame without measurements gives (0.0, []) (:527-530). The temperature term and the fusions stay with the
+    caller. pose0s[i] / linearpoints[i]: the initial linear pose and the linearisation pose of frame i; device_guesses: the
+    guess stage as one device call."""
     to = len(trajectory) if to is None else min(len(trajectory), to)
     maps, _ = LeaveOneOutMaps(nav, trajectory, factors, to=to)
     seen = [i for i in range(to) if len(np.asarray(factors[i][1], float).reshape(-1, 3)) > 0]
-    fits = GuidedFitMixtures(nav, [pose0s[i] for i in seen], [factors[i][1] for i in seen], [maps[i] for i in seen],
-                             [linearpoints[i] for i in seen], average_mode)
+    fits = GuidedFitMixturesRouted(nav, [pose0s[i] for i in seen], [factors[i][1] for i in seen], [maps[i] for i in seen],
+                                   [linearpoints[i] for i in seen], average_mode, None, device_guesses)
     out = [(0.0, []) for _ in range(to)]
     for i, fit in zip(seen, fits):
         out[i] = fit
     return out
+
+
+def MapMessageMixtures(nav, trajectory, factors, pose0s, linearpoints, to=None, average_mode=0):
+    """MapMessageMixturesRouted with the guesses made on the host"""
+    return MapMessageMixturesRouted(nav, trajectory, factors, pose0s, linearpoints, to, average_mode, False)
 
 
 # ---------------------------------------------------------------------------------------------- Filter / FilterMissing

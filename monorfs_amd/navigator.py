@@ -487,6 +487,48 @@ class PHDNavigator:
         """QuasiSetLogLikelihoodGradient for poses of many problems in one launch: (values[n], gradients[n][6])."""
         return self._quasi_batch_multi(problems, poses, problem, average_mode, True)
 
+    def QuasiGuessesMulti(self, problems, pose0s, radius=0.5):
+        """The starting guesses of GuidedFitMixture (LoopyPHDNavigator.cs:789-797) for many problems and their first values
+        (phd_quasi_guesses_multi): problems is a list of (landmarks, measurements, linearpoint), problem q starts at the linear
+        pose pose0s[q]. Returns (offsets[len(problems) + 1], pairs[n][2], guesses6[n][6], poses7[n][7], values[n],
+        emptyspace[len(problems)]): the guesses of problem q stand at offsets[q] .. offsets[q + 1], pose0s[q] first (pair -1, -1),
+        then the (landmark, measurement) pairs within `radius` of the initial pose in landmark-major order; poses7 =
+        Add(linearpoint, guess), values = QuasiSetLogLikelihood there, emptyspace[q] = the value of the pose far from everything.
+        A C call takes problems of one measurement-block class: the problems are split by class, a call that reports more
+        guesses than its arrays hold is repeated once with the reported total, and the results come back in the caller's order."""
+        lms, zs, lins = self._problem_table(problems)
+        pose0s = np.ascontiguousarray(pose0s, np.float64).reshape(-1, 6)
+        T = len(problems)
+        if len(pose0s) != T or any(lin is None for lin in lins):
+            raise ValueError("one initial pose and one linearisation pose per problem")
+        far7 = pose3d_add(np.array([0, 0, 0, 1.0, 0, 0, 0]), np.full(6, 1e5))   # the pose far from everything (:808)
+        per = [None] * T
+        empty = np.zeros(T)
+        for used in self._multi_calls(zs, list(range(T)), max(T, 1)):
+            lmoff, lm, zoff, z, lin, _ = self._pack_problems(lms, zs, lins, used)
+            start = np.ascontiguousarray(pose0s[used])
+            k = len(used)
+            goff, e = np.zeros(k + 1, np.int32), np.zeros(k)
+            capacity = k + min(sum(len(lms[q]) * len(zs[q]) for q in used), 64 * k)   # (every pair, or a first try of 64 a problem)
+            for attempt in (0, 1):
+                pairs, g6, p7, v = np.zeros((capacity, 2), np.int32), np.zeros((capacity, 6)), np.zeros((capacity, 7)), np.zeros(capacity)
+                rc = self._lib.phd_quasi_guesses_multi(self._h, k, lmoff.ctypes.data_as(ip), _ptr(lm) if len(lm) else None,
+                                                       zoff.ctypes.data_as(ip), _ptr(z) if len(z) else None, _ptr(lin), _ptr(start), _ptr(far7),
+                                                       float(radius), capacity, goff.ctypes.data_as(ip), pairs.ctypes.data_as(ip),
+                                                       _ptr(g6), _ptr(p7), _ptr(v), _ptr(e))
+                if rc != PHD_ERR_CAPACITY or attempt:
+                    break
+                capacity = int(goff[k])   # (guess_offsets is set: the total the retry needs)
+            self._check(rc)
+            for j, q in enumerate(used):
+                per[q] = slice(int(goff[j]), int(goff[j + 1])), pairs, g6, p7, v
+                empty[q] = e[j]
+        offsets = np.zeros(T + 1, np.int32)
+        for q in range(T):
+            offsets[q + 1] = offsets[q] + (per[q][0].stop - per[q][0].start)
+        cat = lambda i, tail, dtype: (np.concatenate([per[q][i][per[q][0]] for q in range(T)]) if T else np.zeros((0,) + tail, dtype))
+        return offsets, cat(1, (2,), np.int32), cat(2, (6,), np.float64), cat(3, (7,), np.float64), cat(4, (), np.float64), empty
+
     def LogLikeGradient(self, pose, measurements, landmarks, linearpoint):
         """≙ LoopyPHDNavigator.LogLikeGradient (LoopyPHDNavigator.cs:876-909): central differences (eps = 1e-5) of the
         quasi set log-likelihood at linearpoint.Add(pose +- eps e_i) — the 12 evaluations go to the device as one batch.
